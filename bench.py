@@ -7,7 +7,11 @@ One "step" = the whole hot path on inputs already resident in HBM:
 value = algorithmic fp64 flops of that path (N^3/3 + N^2/2 + N/6 for the Cholesky,
 N^2*n for the triangular solve of K_s) / wall time, whole job, in TFLOP/s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size N] [--dim d] [--ntest n]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size N] [--dim d] [--ntest n] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, what the last of them handed its caller -- lml, mu, var (the predictive
+variance), alpha -- is written as DIR/<name>.npy in float64.  The inputs come from a fixed seed, so two builds run with
+the same arguments can be compared output for output.
 
 --gpus N > 1: one process per GPU over RCCL.  Under torch.distributed.run (RANK / WORLD_SIZE in the
 environment) this process is one rank; started plainly, it spawns the N ranks itself as fresh child
@@ -35,8 +39,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # the pool's host driver only supports dmabuf IPC (RCCL / cross-process device memory)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# hardware queues per stream-priority level (gaussian_process_amd/_lib.py says why); before anything initialises HIP
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 # BASELINE.json's metric, verbatim (it names two quantities: `value` carries the TFLOP/s, `seconds` the time)
 BASELINE_METRIC = "GP-fit+predict sec and achieved fp64 TFLOP/s, N=65536 d=8, 1/2/4/8 MI355X"
@@ -68,6 +70,23 @@ TRAFFIC_KERNEL_SOURCE = os.path.join("gaussian_process_amd", "csrc", "gemm_dma.h
 KBUILD_VALU_PER_ELEMENT_D8 = 36.9
 KBUILD_VALU_PROFILE = os.path.join("profiles", "r03b_kbuild_valu.json")      # the count with the SHA-256 of rbf.hip it was taken on
 CPU_HEADLINE_PROFILE = os.path.join("profiles", "cpu_baseline_measured_headline.json")
+# --dump-outputs: bound on the bytes written, and the seed of the element sample taken when the outputs exceed it
+DUMP_BYTES_MAX = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240531
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy in float64.  Past DUMP_BYTES_MAX in all, every array keeps its share of the
+    bound as a seeded choice of its elements, in index order: the same elements for every build at the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, a.size * DUMP_BYTES_MAX // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kbuild_valu_count():
@@ -509,7 +528,13 @@ def main():
     ap.add_argument("--replay-rank", default=None,
                     help="rehearsal: comma-separated ranks of a --of G run to replay alone on this GPU")
     ap.add_argument("--of", type=int, default=8, help="world size of the replayed run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write lml, mu, var and alpha of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.replay_rank is not None:
+        ap.error("--dump-outputs belongs to the bench line, not to a --replay-rank rehearsal")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))      # before torch / HIP are imported in this process
@@ -691,6 +716,8 @@ def main():
                 stage[k] = stage.get(k, 0.0) + v
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:       # every rank holds the whole result (DistGP gathers it)
+        dump_outputs(args.dump_outputs, {"lml": lml, "mu": mu, "var": var, "alpha": alpha})
     per_rank = None
     if multi:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)

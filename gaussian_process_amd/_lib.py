@@ -11,11 +11,10 @@ import os
 
 import numpy as np
 
-# The HIP runtime maps streams onto a pool of hardware queues per priority level, 4 by default: the fifth stream of a level
-# that gets used shares a queue with an earlier one and their kernels run one after the other (profiles/r04_stream_overlap.txt;
-# it cost a second DistGP instance 20 % before its streams were shared).  Eight per level leaves room for three batch lanes,
-# a context and the partitioned driver in one process.  Read by the runtime when it initialises: set before the first HIP call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The HIP runtime maps streams onto a pool of hardware queues per priority level (GPU_MAX_HW_QUEUES, read when it
+# initialises): a stream beyond the pool's size shares a queue with an earlier one and their kernels run one after the
+# other (profiles/r04_stream_overlap.txt).  The library does not raise that limit: a card has a fixed number of queue
+# slots shared by every process on it, so the pool size is left to the machine's environment.
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgpmi355x.so")

@@ -81,7 +81,12 @@ def main():
     np.savez(out + "_rank%d.npz" % rank, lml=lml, mu=mu, var=var, lml2=lml2, mu2=mu2, sd2=sd2, raised=raised,
              blml=blml, bst=bst, triples=triples, alpha=alpha, Lp=Lp, d_mu=d_mu, d_sd=d_sd, d_fp=d_fp, d_lml=d_lml,
              d_cml=d_cml, g_l=g_l, g_s=g_s, lml1=lml1, mu1=mu1, var1=var1)
-    dist.barrier()
+    # closing rendezvous; on the CPU path an all-reduce of a CPU tensor, because dist.barrier() asks torch for the
+    # accelerator, which initialises the HIP runtime and opens the GPU in every rank
+    if device == "cpu":
+        dist.all_reduce(torch.zeros(1))
+    else:
+        dist.barrier()
     dist.destroy_process_group()
 
 

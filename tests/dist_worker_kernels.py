@@ -53,7 +53,12 @@ def main():
         res["grad_refused"] = 1
     gp.set_kernel("rbf")
     np.savez(out + "_rank%d.npz" % rank, **res)
-    dist.barrier()
+    # closing rendezvous; on the CPU path an all-reduce of a CPU tensor, because dist.barrier() asks torch for the
+    # accelerator, which initialises the HIP runtime and opens the GPU in every rank
+    if device == "cpu":
+        dist.all_reduce(torch.zeros(1))
+    else:
+        dist.barrier()
     dist.destroy_process_group()
 
 

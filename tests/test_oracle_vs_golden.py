@@ -171,13 +171,18 @@ def test_co2_composite_kernel_and_paths(oracle):
     assert np.array_equal(K[:16, :16], g["co2_K_corner"]) and np.array_equal(K[-1], g["co2_K_lastrow"])
     assert np.array_equal(oracle.co2_covariance_function(X, Xs, th), g["co2_Ks"])
     assert np.array_equal(oracle.co2_covariance_function(X[:48], Xs, th), g["co2_Ksq"])     # square: delta added
-    assert oracle.co2_compute_mar_likelihood(X, y, th) == float(g["co2_lml"])
+    # what goes through LAPACK / BLAS (Cholesky, inverse, products) is bit-identical only on the host that made the
+    # vectors -- OpenBLAS picks its kernels by CPU model -- so it gets the module's cross-host slack
+    lml = float(g["co2_lml"])
+    assert abs(oracle.co2_compute_mar_likelihood(X, y, th) - lml) <= LML_RTOL * abs(lml)
     np.random.seed(31)
     mu, sd, fp = oracle.co2_make_prediction(X, Xs, y, th)
-    assert np.array_equal(mu, g["co2_mu"]) and np.array_equal(sd, g["co2_sd"], equal_nan=True)
-    assert np.array_equal(fp, g["co2_fpost"])
+    assert np.allclose(mu, g["co2_mu"], rtol=0, atol=MU_ATOL * np.abs(g["co2_mu"]).max())
+    assert np.allclose(sd, g["co2_sd"], rtol=0, atol=SD_ATOL, equal_nan=True)
+    assert np.allclose(fp, g["co2_fpost"], rtol=0, atol=FPOST_ATOL * np.abs(g["co2_fpost"]).max())
     mu, sd = oracle.co2_bayesian_opt(g["co2_hp"], g["co2_hq"], g["co2_hp_lml"])
-    assert np.array_equal(mu, g["co2_bo_mu"]) and np.array_equal(sd, g["co2_bo_sd"], equal_nan=True)
+    assert np.allclose(mu, g["co2_bo_mu"], rtol=0, atol=MU_ATOL * np.abs(g["co2_bo_mu"]).max())
+    assert np.allclose(sd, g["co2_bo_sd"], rtol=0, atol=SD_ATOL, equal_nan=True)
     assert np.array_equal(oracle.co2_covariance_function(g["co2_hp"], g["co2_hq"], g["co2_hp"][0]), g["co2_Khp"])
 
 
