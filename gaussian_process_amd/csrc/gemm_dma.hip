@@ -23,6 +23,7 @@
 //   F1.x + read F0 <- stage (c+1)%3, k-pairs 0..3 | F1.y
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "gpmi_internal.h"
 #include "gpmi_plan.h"
@@ -54,6 +55,7 @@ struct GemmDmaDev {
     const int64_t* b_block_off;   // B as a table of row blocks (see GemmArgs), or null
     int b_block_tiles;            // 128-row tiles per block
     int S, logS, SM, SN, tri, nsuper;
+    int pair;                     // 1: the 256 x 128 form (gpmi_plan.h: pair plans)
     // tri == 2: staircase (row map with a host copy): supertile row si holds sprefix[si+1] - sprefix[si]
     // live supertiles, its leftmost ones; only those are enumerated
     int sprefix[DMA_MAX_SM + 1];
@@ -390,6 +392,272 @@ __global__ __launch_bounds__(1024 / MI, (MI == 4) ? 2 : 3) void gemm_nt_dma_kern
 // that a kernel trace lists those launches apart from the in-panel and solve-sweep updates.
 __global__ __launch_bounds__(512, 3) void chol_trailing_update_dma_kernel(const GemmDmaDev p) {
     gemm_nt_dma_body<2, false>(p);
+}
+
+// ---------------------------------------------------------------------------
+// Tall form: one workgroup computes the 256 x 128 block of C made of the tiles (ti, tj) and (ti + 1, tj) of a pair plan
+// (gpmi_plan.h).  8 waves of 64 x 64 (4 x 4 accumulators, two waves per SIMD); per K step every SIMD runs 128 MFMAs
+// behind ONE barrier (the 128 x 128 form: 64), the DMA moves 48 KiB per 2 * 256 * 128 * 16 flop (32 KiB per half that)
+// and a wave reads 256 LDS bytes per MFMA (384).
+//
+// Same LDS image, same fragment maps and, per accumulator, the same MFMAs in the same order as the 128 x 128 form
+// (k-pairs 0..3 .x, .y, then 4..7 .x, .y per K step, from zero, C - acc once): the same bits.
+//
+// Ring of TWO 48 KiB stages (96 KiB, as the 128 x 128 form's three: 64 KiB per CU stay free for the panel kernels).
+// Registers: 128 for the accumulators; the fragments are read into the registers of the ones the current quarter has
+// just used up (a wave never holds more than 1.5 half steps of fragments), so that everything fits in 192 per lane.
+// Order per K step c (per wave), MFMAs in four quarters:
+//   q0 F0.x                           | matrix pipe only
+//   q1 F0.y + read F1 <- stage c%2    | an A fragment as soon as its F0 registers are dead, B fragments between
+//   q2 F1.x, first half               | matrix pipe only; then s_waitcnt vmcnt(0) lgkmcnt(0), s_barrier: every read of
+//                                     | stage c has retired, the DMA of step c + 1 has landed (published)
+//   q2 F1.x, second half + DMA(c+2) -> stage c%2 (a full K step ahead of its barrier)
+//   q3 F1.y + read F0 <- stage (c+1)%2
+// A pair with one dead half (above the diagonal, right of its row band, below the grid): the four waves of that half
+// take part in the DMA and the barriers but neither read fragments nor issue MFMAs nor touch C.  A half below the grid
+// moves rows of the live half instead of rows past the end of A.
+// ---------------------------------------------------------------------------
+constexpr int TALL_TM = 2 * DMA_TM;                                // 256 rows of A per block
+constexpr int TALL_STAGE_SLOTS = (TALL_TM + DMA_TN) * 8;           // 16-byte slots per stage (A then B): 48 KiB
+constexpr int TALL_STAGES = 2;
+constexpr size_t TALL_LDS = (size_t)TALL_STAGES * TALL_STAGE_SLOTS * 16;
+static_assert(TALL_LDS == (size_t)DMA_STAGES * DMA_STAGE_SLOTS * 16, "the tall form keeps the LDS footprint");
+
+template <bool DBG>
+__device__ __forceinline__ void gemm_nt_dma_tall_body(const GemmDmaDev& p) {
+    constexpr int DPW = 6;                          // DMA wave-instructions per wave per K step: 4 of A rows, 2 of B rows
+    const int dbg = DBG ? p.dbg : 0;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x;
+    int ti = 0, tj = 0;
+    if (!dma_block_to_tile(p, blockIdx.x, ti, tj)) return;
+    bool l0, l1;
+    plan_pair_live(p, ti, tj, p.row_ncols, l0, l1);
+    // wave-uniform (the map goes through a float square root): scalar registers and scalar branches
+    ti = __builtin_amdgcn_readfirstlane(ti);
+    tj = __builtin_amdgcn_readfirstlane(tj);
+    const bool live0 = __builtin_amdgcn_readfirstlane(l0 ? 1 : 0) != 0;
+    const bool live1 = __builtin_amdgcn_readfirstlane(l1 ? 1 : 0) != 0;
+    if (!live0 && !live1) return;
+    unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
+    if (DBG && (dbg & 16)) st0 = clock64();
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool mine = (wave >> 2) ? live1 : live0;  // this wave's half of the block is live
+    const int wr = (wave >> 1) * 64;
+    const int wc = (wave & 1) * 64;
+    const int fr = lane & 15;
+    const int fg = lane >> 4;
+
+    // ---- DMA: wave w moves A rows 32w..32w+31 and B rows 16w..16w+15, 8 rows per instruction; lane l -> row 8i + (l>>3),
+    // k-pair (l&7)^(row&7).  The lower half of a pair at the bottom edge of the grid reads the upper half's rows again.
+    const int drow = lane >> 3;
+    const int dkp = (lane & 7) ^ (drow & 7);
+    // (wave-uniform row bases in scalar registers, one 32-bit lane offset per operand: two VGPRs instead of six pointers)
+    const int arow = 32 * wave - ((ti + 1 >= p.Tm && wave >= 4) ? DMA_TM : 0);
+    const double* a_row = p.A + ((int64_t)ti * DMA_TM + arow) * p.lda;
+    int64_t b_row0 = (int64_t)tj * DMA_TN * p.ldb;
+    if (p.b_block_off) {                 // wave-uniform: one scalar load
+        const int blk = tj / p.b_block_tiles;
+        b_row0 = p.b_block_off[blk] + (int64_t)(tj - blk * p.b_block_tiles) * DMA_TN * p.ldb;
+    }
+    const double* b_row = p.B + b_row0 + (int64_t)(16 * wave) * p.ldb;
+    const unsigned a_lane = (unsigned)((drow * p.lda + dkp * 2) * 8);      // bytes; drow < 8
+    const unsigned b_lane = (unsigned)((drow * p.ldb + dkp * 2) * 8);
+    const int64_t a_step = 8 * p.lda, b_step = 8 * p.ldb;
+    GPMI_LDS char* lds = (GPMI_LDS char*)smem_raw;
+    const int a_dst = (32 * wave) * 128;
+    const int b_dst = TALL_TM * 128 + (16 * wave) * 128;
+    // (the lane offset goes through a laundered copy: hoisted out of the K loop, the six addresses are twelve VGPRs)
+    auto issue_dma_one = [&](int chunk, int q) {
+        GPMI_LDS char* base = lds + (chunk & 1) * (TALL_STAGE_SLOTS * 16);
+        const int k0 = chunk * 16;
+        unsigned off = q < 4 ? a_lane : b_lane;
+        asm volatile("" : "+v"(off));
+        if (q < 4)
+            __builtin_amdgcn_global_load_lds((const GPMI_GLB void*)((const char*)(a_row + q * a_step + k0) + off),
+                                             (GPMI_LDS void*)(base + a_dst + q * 1024), 16, 0, 0);
+        else
+            __builtin_amdgcn_global_load_lds((const GPMI_GLB void*)((const char*)(b_row + (q - 4) * b_step + k0) + off),
+                                             (GPMI_LDS void*)(base + b_dst + (q - 4) * 1024), 16, 0, 0);
+    };
+
+    // ---- fragment reads: slot row*8 + (kp ^ (row&7)), rows of a fragment differ from fr by multiples of 16
+    const int x7 = fr & 7;
+    const int sl0 = fr * 8 + (fg ^ x7);             // k-pairs 0..3  (F0)
+    const int sl1 = fr * 8 + ((4 + fg) ^ x7);       // k-pairs 4..7  (F1)
+    const d2* smem = reinterpret_cast<const d2*>(smem_raw);
+    auto read_a = [&](int chunk, int half, int i) -> d2 {
+        return smem[(chunk & 1) * TALL_STAGE_SLOTS + (wr + 16 * i) * 8 + (half ? sl1 : sl0)];
+    };
+    auto read_b = [&](int chunk, int half, int j) -> d2 {
+        return smem[(chunk & 1) * TALL_STAGE_SLOTS + TALL_TM * 8 + (wc + 16 * j) * 8 + (half ? sl1 : sl0)];
+    };
+
+    d4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = d4{0., 0., 0., 0.};
+    const int nch = p.nchunks;
+
+#define GPMI_MFMA_X(FA, FB, T) acc[(T) >> 2][(T) & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(FA[(T) >> 2].x, FB[(T) & 3].x, acc[(T) >> 2][(T) & 3], 0, 0, 0)
+#define GPMI_MFMA_Y(FA, FB, T) acc[(T) >> 2][(T) & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(FA[(T) >> 2].y, FB[(T) & 3].y, acc[(T) >> 2][(T) & 3], 0, 0, 0)
+#define GPMI_FENCE() __builtin_amdgcn_sched_barrier(0)
+    // The K loop; LIVE = false: the DMA, waits and barriers only (a dead half)
+    auto kloop = [&](auto live_tag) {
+        constexpr bool LIVE = decltype(live_tag)::value;
+        // ONE set of A fragments (fa[i] is overwritten as soon as the quarter has used it for the last time), two of B
+        d2 fa[4], fb0[4], fb1[4];
+        // prologue: steps 0 and 1 in flight, step 0 landed and published, F0 loaded
+#pragma unroll
+        for (int q = 0; q < DPW; ++q) issue_dma_one(0, q);
+        if (nch > 1) {
+#pragma unroll
+            for (int q = 0; q < DPW; ++q) issue_dma_one(1, q);
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        if constexpr (LIVE) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fa[i] = read_a(0, 0, i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fb0[j] = read_b(0, 0, j);
+        }
+        if (DBG && (dbg & 16)) st1 = clock64();
+        // q0 (F0 .x): matrix pipe only.  It closes the iteration of the step before (the loop runs q1 q2 q3 | q0 of the
+        // next step), so that the fragment reads of q3 and their first uses lie inside one iteration, where the compiler
+        // counts them: the MFMAs wait for their own fragments, not for all of them at the loop head
+        auto quarter0 = [&]() {
+            if constexpr (LIVE) {
+#pragma unroll
+                for (int t = 0; t < 16; ++t) GPMI_MFMA_X(fa, fb0, t);
+                GPMI_FENCE();
+            }
+        };
+        // q1 q2 q3 of step c
+        auto step = [&](int c) {
+            const bool more2 = (c + 2 < nch) && !(dbg & 1);
+            if constexpr (LIVE) {
+                // q1 (F0 .y): F1 <- stage c; A fragment i once row i of the quarter is done, B fragments in between
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    GPMI_MFMA_Y(fa, fb0, 2 * q);
+                    GPMI_MFMA_Y(fa, fb0, 2 * q + 1);
+                    GPMI_FENCE();
+                    if (q & 1) fa[q >> 1] = read_a(c, 1, q >> 1);
+                    else fb1[q >> 1] = read_b(c, 1, q >> 1);
+                    GPMI_FENCE();
+                }
+                // q2 (F1 .x), first half
+#pragma unroll
+                for (int t = 0; t < 8; ++t) GPMI_MFMA_X(fa, fb1, t);
+                GPMI_FENCE();
+            }
+            if (!(dbg & 2)) {
+                asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            GPMI_FENCE();
+            if constexpr (LIVE) {
+                // q2 (F1 .x), second half: the DMA of step c + 2 into the stage of step c
+#pragma unroll
+                for (int t = 8; t < 16; ++t) {
+                    GPMI_MFMA_X(fa, fb1, t);
+                    GPMI_FENCE();
+                    if (more2 && t - 8 < DPW) issue_dma_one(c + 2, t - 8);
+                    GPMI_FENCE();
+                }
+                // q3 (F1 .y): F0 <- stage c + 1 (published by the barrier above), in the same order as in q1.  Also on the
+                // last step (the stage is inside the ring, the values are not used): unconditional reads let the compiler
+                // count them, so the first MFMAs of the next step wait for their own fragments only
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    GPMI_MFMA_Y(fa, fb1, 2 * q);
+                    GPMI_MFMA_Y(fa, fb1, 2 * q + 1);
+                    GPMI_FENCE();
+                    if (q & 1) fa[q >> 1] = read_a(c + 1, 0, q >> 1);
+                    else fb0[q >> 1] = read_b(c + 1, 0, q >> 1);
+                    GPMI_FENCE();
+                }
+            } else if (more2) {
+#pragma unroll
+                for (int q = 0; q < DPW; ++q) issue_dma_one(c + 2, q);
+            }
+        };
+        quarter0();
+        for (int c = 0; c + 1 < nch; ++c) {
+            step(c);
+            quarter0();
+        }
+        step(nch - 1);
+    };
+    if (mine) kloop(std::true_type{});
+    else kloop(std::false_type{});
+#undef GPMI_MFMA_X
+#undef GPMI_MFMA_Y
+#undef GPMI_FENCE
+    if (!mine) return;
+
+    if (DBG && (dbg & 16)) st2 = clock64();
+    // epilogue: C -= acc in 16-row bands.  The fragments' registers hold one band: band 0 alone, then (with band 0's
+    // accumulators free) bands 1 and 2 together, band 3 behind the stores of band 1
+    double* Cg = p.C + ((int64_t)ti * DMA_TM + wr) * p.ldc + (int64_t)tj * DMA_TN + wc;
+    auto c_ptr = [&](int i, int j, int v) { return Cg + (int64_t)(16 * i + 4 * v + fg) * p.ldc + 16 * j + fr; };
+    if (DBG && (dbg & 8)) {
+        double t = 0.;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
+        if (t == 123.456) Cg[0] = t;
+        return;
+    }
+    double cv[2][4][4];
+    auto load_band = [&](int i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) cv[i & 1][j][v] = *c_ptr(i, j, v);
+    };
+    auto store_band = [&](int i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) *c_ptr(i, j, v) = cv[i & 1][j][v] - acc[i][j][v];
+    };
+    load_band(0);
+    if (DBG && (dbg & 16)) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        st3 = clock64();
+    }
+    store_band(0);
+    load_band(1);
+    load_band(2);
+    store_band(1);
+    load_band(3);
+    store_band(2);
+    store_band(3);
+    if (DBG && (dbg & 16)) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long st4 = clock64();
+        if (lane == 0 && blockIdx.x < 4096) {
+            unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 4 + (wave & 3)) * 4;
+            o[0] = st1 - st0; o[1] = st2 - st1; o[2] = st3 - st2; o[3] = st4 - st3;
+        }
+    }
+}
+
+// 512 threads, two waves per SIMD, at most 192 VGPR + AGPR per lane: 128 per SIMD lane stay for a panel kernel's wave
+template <bool DBG>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(192))) void gemm_nt_dma_tall_kernel(const GemmDmaDev p) {
+    gemm_nt_dma_tall_body<DBG>(p);
+}
+// the trailing update's own symbol (GemmArgs::role == 1), as chol_trailing_update_dma_kernel for the 128 x 128 form
+__global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(192))) void chol_trailing_update_dma256_kernel(const GemmDmaDev p) {
+    gemm_nt_dma_tall_body<false>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -921,6 +1189,7 @@ hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a) {
                     p.row_block_tiles, 0, tn.gemm_balance != 0))
         return hipErrorInvalidValue;
     p.S = plan.S; p.logS = plan.logS; p.SM = plan.SM; p.SN = plan.SN; p.tri = plan.tri; p.nsuper = plan.nsuper;
+    p.pair = 0;
     if (plan.tri == 2) std::copy(plan.sprefix, plan.sprefix + plan.SM + 1, p.sprefix);
     const int nblocks = plan.nblocks;
     constexpr size_t lds = (size_t)DMA_STAGES * DMA_STAGE_SLOTS * 16;
@@ -961,6 +1230,33 @@ hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a) {
         constexpr size_t ldsp = lds + 16;          // ring + mailbox
         if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_persist_kernel, dim3(pool->groups), dim3(512), ldsp, s, p);
         else hipLaunchKernelGGL(gemm_nt_dma_persist_kernel, dim3(pool->groups), dim3(512), ldsp, s, p);
+        return hipGetLastError();
+    }
+    // tall form (option gemm_tall): 256 x 128 blocks for launches of at least tall_min_tiles live tiles, as a pair plan
+    // with the same supertiles; its own kernel symbol for the trailing updates
+    if (tn.gemm_dma_waves == 8 && tn.gemm_tall &&
+        plan_live_tiles(p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols_host, a.row_bands, p.row_block_tiles) >= tn.tall_min_tiles) {
+        TilePlan pp;
+        if (!plan_tiles(pp, p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols != nullptr, a.row_ncols_host, a.row_bands,
+                        p.row_block_tiles, 0, tn.gemm_balance != 0, true))
+            return hipErrorInvalidValue;
+        p.S = pp.S; p.logS = pp.logS; p.SM = pp.SM; p.SN = pp.SN; p.tri = pp.tri; p.nsuper = pp.nsuper; p.pair = 1;
+        if (pp.tri == 2) std::copy(pp.sprefix, pp.sprefix + pp.SM + 1, p.sprefix);
+        p.nblocks = pp.nblocks;
+        static PerDeviceOnce once_tall;
+        const hipError_t et = once_tall.run([&]() -> hipError_t {
+            const void* fns[] = {(const void*)gemm_nt_dma_tall_kernel<false>, (const void*)gemm_nt_dma_tall_kernel<true>,
+                                 (const void*)chol_trailing_update_dma256_kernel};
+            for (const void* f : fns) {
+                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TALL_LDS);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        });
+        if (et != hipSuccess) return et;
+        if (p.dbg) hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<true>, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
+        else if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_dma256_kernel, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
+        else hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<false>, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
         return hipGetLastError();
     }
     if (tn.gemm_dma_waves == 8) {

@@ -115,6 +115,12 @@ static int set_tuning_option(Tuning& t, const char* name, int64_t value) {
     } else if (!strcmp(name, "gemm_dma_waves")) {
         if (value != 4 && value != 8) return fail_arg("gemm_dma_waves must be 4 or 8");
         t.gemm_dma_waves = (int)value;
+    } else if (!strcmp(name, "gemm_tall")) {
+        if (value < 0 || value > 1) return fail_arg("gemm_tall must be 0 (128 x 128 blocks) or 1 (256 x 128 blocks for large launches)");
+        t.gemm_tall = (int)value;
+    } else if (!strcmp(name, "tall_min_tiles")) {
+        if (value < 0 || value > (1 << 30)) return fail_arg("tall_min_tiles must be in 0..2^30");
+        t.tall_min_tiles = (int)value;
     } else if (!strcmp(name, "gemm_dma")) {
         t.gemm_use_dma = value ? 1 : 0;
     } else {

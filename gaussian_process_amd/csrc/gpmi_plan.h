@@ -25,6 +25,8 @@ constexpr int DMA_MAX_SM = 128;     // supertile rows a staircase launch can des
 // The enumeration of one launch: blocks b = 0 .. nblocks - 1; block b belongs to XCD group b % 8 (the hardware deals
 // workgroups round-robin over the 8 XCDs), blocks 8 w + x with equal w / S^2 form supertile (w / S^2) * 8 + x: S x S
 // tiles that share A rows and B rows in that XCD's L2.
+// Pair plans (pair = 1, the 256 x 128 form of gemm_dma.hip): a block is the PAIR of row tiles (ti, tj), (ti + 1, tj) with
+// ti even; the supertiles, their order and their deal to the XCDs are the 128-tile plan's, each holds S^2 / 2 blocks.
 struct TilePlan {
     int Tm = 0, Tn = 0;             // tiles
     int lower = 0;                  // skip tiles entirely above {col <= row + diag_off}
@@ -34,16 +36,18 @@ struct TilePlan {
     int tri = 0;                    // 0 rectangle (columns rotated by the supertile row), 1 lower triangle of supertiles, 2 staircase
     int nsuper = 0;
     int nblocks = 0;
+    int pair = 0;                   // 1: blocks are pairs of vertically adjacent tiles (S >= 2)
     int sprefix[DMA_MAX_SM + 1];    // tri == 2: supertile row si holds its leftmost sprefix[si + 1] - sprefix[si] supertiles
     const int32_t* row_ncols = nullptr;   // tri == 2: the row map (host copy here; the kernels' struct holds the device copy)
 };
 
-// block number -> tile; false: the block lies outside the tile grid (padding of the enumeration)
+// block number -> tile (pair plans: the upper tile of the pair); false: the block lies outside the tile grid (padding of
+// the enumeration)
 template <class PT>
 GPMI_HD bool plan_block_to_tile(const PT& p, int b, int& ti, int& tj) {
     const int xcd = b & 7;
     const int w = b >> 3;
-    const int S2 = p.S * p.S;
+    const int S2 = (p.S * p.S) >> p.pair;           // blocks per supertile
     const int s = (w / S2) * 8 + xcd;
     if (s >= p.nsuper) return false;
     const int q = w % S2;
@@ -56,16 +60,18 @@ GPMI_HD bool plan_block_to_tile(const PT& p, int b, int& ti, int& tj) {
             // the LAST live supertile of a staircase row is ragged (a row block's own diagonal block: its lower triangle):
             // its live tiles first, row by row, the dead blocks behind them -- consecutive blocks go to the XCD's four
             // shader engines in turn, and as a square the engine with the supertile's first columns carried most of it
+            // (pair plans: row pairs, each as wide as the wider of its two rows)
             int acc = 0;
-            for (int r = 0; r < p.S; ++r) {
-                const int tr = si * p.S + r;
+            for (int r = 0; r < (p.S >> p.pair); ++r) {
+                const int tr = si * p.S + (r << p.pair);
                 int w = 0;
-                if (tr < p.Tm) {
-                    const int64_t nc = p.row_ncols[tr / p.row_block_tiles];
+                for (int h = 0; h <= p.pair; ++h) {
+                    if (tr + h >= p.Tm) break;
+                    const int64_t nc = p.row_ncols[(tr + h) / p.row_block_tiles];
                     int64_t wl = (nc + PLAN_TILE - 1) / PLAN_TILE - (int64_t)sj * p.S;
                     if (wl > p.S) wl = p.S;
                     if (wl > (int64_t)p.Tn - (int64_t)sj * p.S) wl = (int64_t)p.Tn - (int64_t)sj * p.S;
-                    w = wl > 0 ? (int)wl : 0;
+                    if (wl > w) w = (int)wl;
                 }
                 if (q < acc + w) {
                     ti = tr;
@@ -91,6 +97,16 @@ GPMI_HD bool plan_block_to_tile(const PT& p, int b, int& ti, int& tj) {
         sj += si % p.SN;
         if (sj >= p.SN) sj -= p.SN;
     }
+    if (p.tri == 1 && si == sj && p.pair) {
+        // the same for a pair plan: row pair r (tile rows 2r, 2r + 1) holds 2r + 2 live pairs, r (r + 1) before it
+        int r = (int)((sqrtf(4.f * (float)q + 1.f) - 1.f) * 0.5f);
+        while ((r + 1) * (r + 2) <= q) ++r;
+        while (r * (r + 1) > q) --r;
+        if (2 * r >= p.S) return false;
+        ti = si * p.S + 2 * r;
+        tj = sj * p.S + (q - r * (r + 1));
+        return ti < p.Tm && tj < p.Tn;
+    }
     if (p.tri == 1 && si == sj) {
         // A supertile ON the diagonal holds S (S + 1) / 2 live tiles.  They are enumerated FIRST, in row-major order of the
         // lower triangle, the dead blocks after them: inside an XCD consecutive blocks go to its four shader engines in
@@ -104,7 +120,7 @@ GPMI_HD bool plan_block_to_tile(const PT& p, int b, int& ti, int& tj) {
         tj = sj * p.S + (q - r * (r + 1) / 2);
         return ti < p.Tm && tj < p.Tn;
     }
-    ti = si * p.S + (q >> p.logS);
+    ti = si * p.S + ((q >> p.logS) << p.pair);
     tj = sj * p.S + (q & (p.S - 1));
     return ti < p.Tm && tj < p.Tn;
 }
@@ -124,6 +140,13 @@ GPMI_HD bool plan_tile_live(const PT& p, int ti, int tj, const int32_t* row_ncol
     return true;
 }
 
+// a block of a pair plan: tile ti (its upper half) and tile ti + 1 (its lower half, if inside the grid) -- live halves
+template <class PT>
+GPMI_HD void plan_pair_live(const PT& p, int ti, int tj, const int32_t* row_ncols, bool& live0, bool& live1) {
+    live0 = plan_tile_live(p, ti, tj, row_ncols);
+    live1 = ti + 1 < p.Tm && plan_tile_live(p, ti + 1, tj, row_ncols);
+}
+
 // How a launch of one workgroup per tile is dealt out (measured, round 4: profiles/r04_resident_cost_count.txt): block b
 // goes to XCD b % 8, and inside the XCD consecutive blocks go to its four shader engines in turn -- engine ((b >> 3) % 4) --,
 // each of which places them on its own 8 CUs as they become free.  Nothing is balanced ACROSS engines: the launch lasts as
@@ -138,27 +161,34 @@ GPMI_HD bool plan_tile_live(const PT& p, int ti, int tj, const int32_t* row_ncol
 // host); has_row_map: the launch has a device row map (with or without a host copy).  force_S != 0 pins the supertile
 // edge (tests).  balance_xcds: the launch is one workgroup per tile, dealt statically to the XCDs -- pick the supertile
 // edge with the deal in mind (the resident forms draw tiles from counters and take over each other's tails: they keep
-// the widest supertile).  Returns false when the arguments are unusable.
+// the widest supertile).  pair: plan pairs of row tiles (the 256 x 128 form).  Returns false when the arguments are
+// unusable.
 inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t diag_off, bool has_row_map,
                        const int32_t* row_ncols_host, int row_bands, int row_block_tiles, int force_S = 0,
-                       bool balance_xcds = true);
+                       bool balance_xcds = true, bool pair = false);
 
+// Pair plans: a block holds a CU for two tiles' time whether one or both of its halves are live, so the rounds count
+// blocks and the work counts live tiles at half a block each.
 inline double plan_xcd_efficiency(const TilePlan& p, const int32_t* row_ncols_host, int cus_per_engine = 8) {
     long load[32];
     for (int x = 0; x < 32; ++x) load[x] = 0;
     long total = 0;
     for (int b = 0; b < p.nblocks; ++b) {
         int ti, tj;
-        if (plan_block_to_tile(p, b, ti, tj) && plan_tile_live(p, ti, tj, row_ncols_host)) { ++load[b & 31]; ++total; }
+        if (!plan_block_to_tile(p, b, ti, tj)) continue;
+        bool l0, l1 = false;
+        if (p.pair) plan_pair_live(p, ti, tj, row_ncols_host, l0, l1);
+        else l0 = plan_tile_live(p, ti, tj, row_ncols_host);
+        if (l0 || l1) { ++load[b & 31]; total += (long)l0 + (long)l1; }
     }
     long rounds = 0;
     for (int x = 0; x < 32; ++x) rounds = std::max(rounds, (load[x] + cus_per_engine - 1) / cus_per_engine);
-    return rounds ? (double)total / (32.0 * cus_per_engine) / (double)rounds : 1.0;
+    return rounds ? (double)total / (32.0 * cus_per_engine * (1 + p.pair)) / (double)rounds : 1.0;
 }
 
 inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t diag_off, bool has_row_map,
                        const int32_t* row_ncols_host, int row_bands, int row_block_tiles, int force_S,
-                       bool balance_xcds) {
+                       bool balance_xcds, bool pair) {
     if (Tm <= 0 || Tn <= 0 || Tm > (1 << 20) || Tn > (1 << 20)) return false;
     if (row_ncols_host && row_bands <= 0) return false;
     p.Tm = (int)Tm; p.Tn = (int)Tn;
@@ -166,6 +196,7 @@ inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t d
     p.row_block_tiles = row_block_tiles > 0 ? row_block_tiles : 1;
     p.tri = (lower && diag_off == 0 && 2 * p.Tn >= p.Tm) ? 1 : 0;
     p.row_ncols = nullptr;
+    p.pair = pair ? 1 : 0;
     const bool stairs = has_row_map && row_ncols_host && row_bands > 0 && !lower;
     // supertile edge: 8 tiles, but never wider than the launch -- a strip of Tn = 1 (a panel-internal update of 128
     // columns) enumerated in 8 x 8 supertiles is seven dead workgroups for every live one, and a dead workgroup still has
@@ -173,6 +204,9 @@ inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t d
     // each of them waits for a tile to finish)
     int S = 8;
     while (S > 1 && (S > p.Tn || S > p.Tm)) S >>= 1;
+    const int min_S = pair ? 2 : 1;                 // a pair plan's supertile holds whole pairs
+    if (S < min_S) S = min_S;
+    if (force_S && force_S < min_S) return false;
     // mid-size triangular launches: the largest supertile edge whose deal to the XCDs is within 1 % of the best one
     // (plan_tri_xcd_efficiency); never below 2 (an edge of 1 gives up all reuse of the operands in an XCD's L2)
     // a rank's staircase of row blocks (row map with a host copy) and mid-size triangular launches: the widest edge whose
@@ -184,7 +218,7 @@ inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t d
         int cand[4], nc = 0;
         for (int c = S; c >= 2 && nc < 4; c >>= 1) {
             TilePlan q;
-            if (!plan_tiles(q, Tm, Tn, lower, diag_off, has_row_map, row_ncols_host, row_bands, row_block_tiles, c, false)) break;
+            if (!plan_tiles(q, Tm, Tn, lower, diag_off, has_row_map, row_ncols_host, row_bands, row_block_tiles, c, false, pair)) break;
             if (stairs && q.tri != 2) break;             // the staircase table does not hold this edge
             cand[nc] = c;
             eff[nc] = plan_xcd_efficiency(q, row_ncols_host);
@@ -217,15 +251,35 @@ inline bool plan_tiles(TilePlan& p, int64_t Tm, int64_t Tn, int lower, int64_t d
             ns = tot;
             use_stairs = true;
         }
-        if (ns >= 32 || S == 1 || force_S) {
+        if (ns >= 32 || S == min_S || force_S) {
             p.S = S; p.SM = SM; p.SN = SN; p.nsuper = ns;
             if (use_stairs) { p.tri = 2; p.row_ncols = row_ncols_host; }
             break;
         }
     }
     p.logS = (p.S == 8) ? 3 : (p.S == 4) ? 2 : (p.S == 2) ? 1 : 0;
-    p.nblocks = ((p.nsuper + 7) / 8) * 8 * p.S * p.S;
+    p.nblocks = ((p.nsuper + 7) / 8) * 8 * ((p.S * p.S) >> p.pair);
     return true;
+}
+
+// live 128-tiles of a launch (without a host copy of its row map every tile in the row band's reach counts)
+inline int64_t plan_live_tiles(int64_t Tm, int64_t Tn, int lower, int64_t diag_off, const int32_t* row_ncols_host,
+                               int row_bands, int row_block_tiles) {
+    int64_t n = 0;
+    const int rbt = row_block_tiles > 0 ? row_block_tiles : 1;
+    for (int64_t ti = 0; ti < Tm; ++ti) {
+        int64_t w = Tn;
+        if (lower) {
+            const int64_t lim = ti * PLAN_TILE + PLAN_TILE - 1 + diag_off;     // tiles tj with tj * 128 <= lim
+            w = lim < 0 ? 0 : std::min<int64_t>(Tn, lim / PLAN_TILE + 1);
+        }
+        if (row_ncols_host && row_bands > 0) {
+            const int64_t nc = row_ncols_host[std::min<int64_t>(ti / rbt, row_bands - 1)];
+            w = std::min<int64_t>(w, nc > 0 ? (nc + PLAN_TILE - 1) / PLAN_TILE : 0);
+        }
+        n += w;
+    }
+    return n;
 }
 
 // Block widths of a blocked sweep over ncols columns at nominal width NB.  ramp (bit mask, only with ramp_ok): 1 ramp up
