@@ -661,14 +661,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(192))) void cho
 }
 
 // ---------------------------------------------------------------------------
-// Ticket form of the 8-wave kernel: gridDim.x = (CUs per XCD - r) x 8 workgroups (one per CU: 96 KiB of LDS each)
-// stay for the whole launch and draw their tiles from the launch's per-XCD counters.  Unlike the persistent form
-// below it keeps NOTHING across tiles -- same registers as the per-tile kernel (the C tile is not prefetched), so
-// the small-LDS panel kernels of the other stream still fit on a CU beside it -- and what it buys is placement:
-//   * r CUs per XCD are never touched by the launch (`reserve`): a panel kernel that needs a whole CU (potrf128:
-//     2 x 123 registers per SIMD lane) finds one at once instead of waiting for the update's next round boundary;
-//   * an XCD whose own blocks are used up draws from the others' counters, so the tail of a launch is shared by
-//     all CUs, not by the CUs of the XCD the static deal left with the most work.
+// Ticket form of the 8-wave kernel: gridDim.x = CUs per XCD x 8 workgroups (one per CU: 96 KiB of LDS each) stay
+// for the whole launch and draw their tiles from the launch's per-XCD counters.  Unlike the persistent form below it
+// keeps NOTHING across tiles -- same registers as the per-tile kernel (the C tile is not prefetched), so the small-LDS
+// panel kernels of the other stream still fit on a CU beside it -- and what it buys is placement: an XCD whose own
+// blocks are used up draws from the others' counters, so the tail of a launch is shared by all CUs, not by the CUs of
+// the XCD the static deal left with the most work.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 3) void gemm_nt_dma_ticket_kernel(const GemmDmaDev p) {
     gemm_nt_dma_body<2, false, true>(p);
@@ -1210,14 +1208,12 @@ hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a) {
     p.slot = nullptr;
     p.nblocks = nblocks;
     // ticket form (option gemm_ticket: 1 for the Cholesky's trailing updates while two streams are busy, 2 for every
-    // launch of at least one round; gemm_reserve CUs per XCD stay untouched)
+    // launch of at least one round)
     if (ticket) {
-        const int reserve = std::max(0, std::min(tn.gemm_reserve, pool->groups / 8 - 1));
         p.slot = pool->next();
-        const int groups = pool->groups - 8 * reserve;
         constexpr size_t ldst = lds + 16;          // ring + mailbox
-        if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_ticket_kernel, dim3(groups), dim3(512), ldst, s, p);
-        else hipLaunchKernelGGL(gemm_nt_dma_ticket_kernel, dim3(groups), dim3(512), ldst, s, p);
+        if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_ticket_kernel, dim3(pool->groups), dim3(512), ldst, s, p);
+        else hipLaunchKernelGGL(gemm_nt_dma_ticket_kernel, dim3(pool->groups), dim3(512), ldst, s, p);
         return hipGetLastError();
     }
     // persistent form: launches with at least two rounds of tiles and a K loop long enough to draw the successor in --

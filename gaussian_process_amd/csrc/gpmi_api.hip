@@ -72,12 +72,11 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
-                       &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside, &c->pmail})
+                       &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
     (void)hipStreamDestroy(c->pstream);
-    if (c->sstream) (void)hipStreamDestroy(c->sstream);
     if (c->vstream) (void)hipStreamDestroy(c->vstream);
     delete c;
     return GPMI_OK;
@@ -96,14 +95,8 @@ static int set_tuning_option(Tuning& t, const char* name, int64_t value) {
     } else if (!strcmp(name, "gemm_ticket")) {
         if (value < 0 || value > 2) return fail_arg("gemm_ticket must be 0 (off), 1 (trailing updates under lookahead) or 2 (every launch)");
         t.gemm_ticket = (int)value;
-    } else if (!strcmp(name, "potrf_server")) {
-        if (value < 0 || value > 1023) return fail_arg("potrf_server: 0 off, 1 on, bits 2..512 timing-only ablations");
-        t.potrf_server = (int)value;
     } else if (!strcmp(name, "gemm_balance")) {
         t.gemm_balance = value ? 1 : 0;
-    } else if (!strcmp(name, "gemm_reserve")) {
-        if (value < 0 || value > 24) return fail_arg("gemm_reserve must be in 0..24 (CUs per XCD)");
-        t.gemm_reserve = (int)value;
     } else if (!strcmp(name, "trsv_vinv")) {
         if (value < 0 || value > 2) return fail_arg("trsv_vinv must be 0 (16 x 16 rounds), 1 (one launch per block) or 2 (one launch)");
         t.trsv_vinv = (int)value;

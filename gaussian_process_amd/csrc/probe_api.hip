@@ -1,7 +1,5 @@
 // Measurement probes of the C-ABI (fp64 MFMA issue rate, GEMM kernel ablations, HBM store patterns):
 // what scripts/probe*.py and the numbers in DESIGN.md section 4 come from.  Not on the product path.
-#include <chrono>
-
 #include "gpmi_ctx.h"
 
 using namespace gpmi;
@@ -286,224 +284,6 @@ int gpmi_probe_trsv_giveup(gpmi_ctx* c, int64_t n, double wait_ms, int* err_out,
     *elapsed_ms = ms;
     L.release(); vs.release(); m.release(); x.release(); err.release();
     return GPMI_OK;
-}
-
-// One resident workgroup that does nothing: `threads` threads and `lds_bytes` of LDS it never touches, asleep for
-// `milliseconds` on a stream of its own (high_priority != 0: the device's highest stream priority).  Returns at once; time
-// something else (gpmi_probe_gemm) while it is resident to see what a workgroup that merely HOLDS a CU costs the rest of the
-// chip (the resident potrf128 chain).
-__global__ void probe_sleeper_kernel(unsigned long long ticks, const unsigned long long* poll, int poll_sleep, int fences) {
-    const unsigned long long t0 = wall_clock64();
-    if (!poll) {
-        while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
-        return;
-    }
-    // the way a flag-chained resident kernel waits: thread 0 re-reads a device flag with agent-scope atomic loads
-    // (poll_sleep = argument of s_sleep between two reads); fences & 1: an agent-scope acquire + release pair every
-    // ~30 us, as a kernel would issue around each unit of work it is released for; fences & 2: the OTHER waves of the
-    // workgroup do not leave but wait at a workgroup barrier for thread 0 (as the waves of a server workgroup wait for
-    // their next job) -- round 4: THAT is what costs a concurrent GEMM 14 %
-    if (threadIdx.x == 0) {
-        unsigned long long acc = 0, last = t0;
-        while (wall_clock64() - t0 < ticks) {
-            acc += __hip_atomic_load(poll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (poll_sleep == 1) __builtin_amdgcn_s_sleep(1);
-            else if (poll_sleep <= 2) __builtin_amdgcn_s_sleep(2);
-            else if (poll_sleep <= 16) __builtin_amdgcn_s_sleep(16);
-            else __builtin_amdgcn_s_sleep(64);
-            if ((fences & 1) && wall_clock64() - last > 3000) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                last = wall_clock64();
-            }
-        }
-        if (acc == 0x123456789ull) __builtin_trap();
-    }
-    if (fences & 2) __syncthreads();
-}
-
-// the same sleeper holding ~130 vector registers per lane (64 doubles kept live across the sleep): what a resident
-// workgroup's REGISTER footprint does to a concurrent GEMM, apart from everything else about it (fences & 4 selects it)
-// park: 0 every wave sleeps in a loop; 1 wave 0 sleeps in a loop, the others wait for it at a workgroup barrier; 2 wave 0
-// sleeps in a loop, the others poll an LDS word it sets at the end (s_sleep between reads)
-}  // extern "C" (a template needs C++ linkage)
-template <int ND>
-__global__ __launch_bounds__(512) void probe_sleeper_fat_kernel(unsigned long long ticks, double* sink, int park) {
-    __shared__ volatile int done;
-    double v[ND];
-#pragma unroll
-    for (int i = 0; i < ND; ++i) v[i] = (double)(threadIdx.x + i);
-#pragma unroll
-    for (int i = 0; i < ND; ++i) asm volatile("" : "+v"(v[i]));
-    if (threadIdx.x == 0) done = 0;
-    __syncthreads();
-    const unsigned long long t0 = wall_clock64();
-    if (park == 0 || threadIdx.x < 64) {
-        while (wall_clock64() - t0 < ticks) {
-            __builtin_amdgcn_s_sleep(64);
-#pragma unroll
-            for (int i = 0; i < ND; ++i) asm volatile("" : "+v"(v[i]));
-        }
-        if (threadIdx.x == 0) done = 1;
-    }
-    if (park == 1) __syncthreads();
-    if (park == 2 && threadIdx.x >= 64) {
-        while (!done) __builtin_amdgcn_s_sleep(64);
-    }
-    double t = 0.;
-#pragma unroll
-    for (int i = 0; i < ND; ++i) t += v[i];
-    if (t == 123.456) sink[0] = t;
-}
-extern "C" {
-
-// streams of sleepers that may still be running: destroyed by a LATER call.  hipStreamDestroy WAITS for the stream's work on
-// this runtime -- until round 4 this probe destroyed the sleeper's stream right after the launch, i.e. it returned when the
-// sleeper was gone, and everything timed "beside" it ran alone (profiles/r03_resident_workgroup_cost.txt is void).
-static std::vector<hipStream_t> g_sleeper_streams;
-
-int gpmi_probe_resident(gpmi_ctx* c, int high_priority, int lds_bytes, int threads, double milliseconds, int poll_sleep,
-                        int fences) {
-    if (!c || lds_bytes < 0 || lds_bytes > 160 * 1024 || threads < 64 || threads > 1024 || threads % 64 ||
-        !(milliseconds > 0.0) || milliseconds > 5000.0)
-        return fail_arg("gpmi_probe_resident: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    // (poll_sleep < 0: keep the earlier sleepers -- several resident at once, each on a stream of its own)
-    if (poll_sleep >= 0) {
-        for (hipStream_t old : g_sleeper_streams) (void)hipStreamDestroy(old);   // waits for sleepers of earlier calls
-        g_sleeper_streams.clear();
-    } else {
-        poll_sleep = 0;
-    }
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    hipStream_t st = nullptr;
-    HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, high_priority ? hi : lo));
-    hipError_t e = hipFuncSetAttribute((const void*)probe_sleeper_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) {
-        const unsigned long long* flag = nullptr;
-        if (poll_sleep > 0) {
-            if (c->red.ensure(16 * 8) != hipSuccess) { (void)hipStreamDestroy(st); return fail_arg("gpmi_probe_resident: no scratch"); }
-            flag = reinterpret_cast<const unsigned long long*>(c->red.as<double>() + 12);
-        }
-        if (fences & 4) {
-            // fences bits 5..6: register footprint -- 0 ~130 per lane, 1 ~138, 2 ~146, 3 ~106
-            const int fat = (fences >> 5) & 3;
-            const void* fn = fat == 1 ? (const void*)probe_sleeper_fat_kernel<68> : fat == 2 ? (const void*)probe_sleeper_fat_kernel<72>
-                           : fat == 3 ? (const void*)probe_sleeper_fat_kernel<52> : (const void*)probe_sleeper_fat_kernel<64>;
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (e == hipSuccess && c->red.ensure(16 * 8) != hipSuccess) e = hipErrorOutOfMemory;
-            if (e == hipSuccess) {
-                const unsigned long long tk = (unsigned long long)(milliseconds * 1e5);
-                double* sink = c->red.as<double>();
-                const int park = (fences >> 3) & 3;
-                if (fat == 1) hipLaunchKernelGGL(probe_sleeper_fat_kernel<68>, dim3(1), dim3((unsigned)threads), (size_t)lds_bytes, st, tk, sink, park);
-                else if (fat == 2) hipLaunchKernelGGL(probe_sleeper_fat_kernel<72>, dim3(1), dim3((unsigned)threads), (size_t)lds_bytes, st, tk, sink, park);
-                else if (fat == 3) hipLaunchKernelGGL(probe_sleeper_fat_kernel<52>, dim3(1), dim3((unsigned)threads), (size_t)lds_bytes, st, tk, sink, park);
-                else hipLaunchKernelGGL(probe_sleeper_fat_kernel<64>, dim3(1), dim3((unsigned)threads), (size_t)lds_bytes, st, tk, sink, park);
-            }
-        } else {
-            hipLaunchKernelGGL(probe_sleeper_kernel, dim3(1), dim3((unsigned)threads), (size_t)lds_bytes, st,
-                               (unsigned long long)(milliseconds * 1e5), flag, poll_sleep, fences);      // wall_clock64: 100 MHz
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    g_sleeper_streams.push_back(st);     // NOT destroyed here: that would wait for the sleeper
-    if (e != hipSuccess) return fail_runtime(e, "probe_sleeper launch");
-    return GPMI_OK;
-}
-
-// A storm of tiny kernels on a stream of its own: `count` launches of a one-wave kernel, `sleep_us` microseconds long
-// each (kind 0: it only sleeps; 1: an agent-scope release + acquire fence pair as well; 2: an agent-scope atomic store
-// as well).  Returns at once; time something else (gpmi_probe_gemm) meanwhile to see what the KERNEL BOUNDARIES of a
-// busy second stream -- the runtime brackets every kernel with cache maintenance -- cost a long-running update GEMM
-// (the resident panel chain of round 3 doubled the launches on the panel stream).
-__global__ void probe_tiny_kernel(unsigned long long ticks, int kind, unsigned long long* flag) {
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-    if (kind == 1 && threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    if (kind == 2 && threadIdx.x == 0) __hip_atomic_store(flag, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-int gpmi_probe_launch_storm(gpmi_ctx* c, int high_priority, int count, double sleep_us, int kind) {
-    if (!c || count < 1 || count > 200000 || sleep_us < 0.0 || sleep_us > 1000.0 || kind < 0 || kind > 2)
-        return fail_arg("gpmi_probe_launch_storm: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->red.ensure(16 * 8));
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    hipStream_t st = nullptr;
-    HIP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, high_priority ? hi : lo));
-    hipError_t e = hipSuccess;
-    unsigned long long* flag = reinterpret_cast<unsigned long long*>(c->red.as<double>() + 12);
-    for (int i = 0; i < count && e == hipSuccess; ++i) {
-        hipLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, st, (unsigned long long)(sleep_us * 100.0), kind, flag);
-        e = hipGetLastError();
-    }
-    (void)hipStreamDestroy(st);          // released when the kernels have finished
-    if (e != hipSuccess) return fail_runtime(e, "probe_tiny launch");
-    return GPMI_OK;
-}
-
-// How many streams of a priority really run side by side?  n_high streams at the device's highest priority and n_norm at
-// the default one, each handed ONE one-wave kernel that sleeps `milliseconds`; *wall_ms = time until all have finished.
-// All concurrent: ~milliseconds; streams that share a hardware queue run one after the other: a multiple of it.  The
-// runtime maps streams onto a small pool of hardware queues as they are first used (a second
-// DistGP instance's fresh pair of auxiliary streams landed on one queue).
-int gpmi_probe_stream_overlap(gpmi_ctx* c, int n_high, int n_norm, double milliseconds, double* wall_ms) {
-    if (!c || !wall_ms || n_high < 0 || n_norm < 0 || n_high + n_norm < 1 || n_high + n_norm > 32 || !(milliseconds > 0.0) ||
-        milliseconds > 1000.0)
-        return fail_arg("gpmi_probe_stream_overlap: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    std::vector<hipStream_t> st((size_t)(n_high + n_norm), nullptr);
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < st.size() && e == hipSuccess; ++i)
-        e = hipStreamCreateWithPriority(&st[i], hipStreamNonBlocking, (int)i < n_high ? hi : lo);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (size_t i = 0; i < st.size() && e == hipSuccess; ++i) {
-        hipLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, st[i], (unsigned long long)(milliseconds * 1e5), 0,
-                           (unsigned long long*)nullptr);
-        e = hipGetLastError();
-    }
-    for (size_t i = 0; i < st.size(); ++i)
-        if (st[i]) { if (e == hipSuccess) e = hipStreamSynchronize(st[i]); }
-    *wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (hipStream_t s : st) if (s) (void)hipStreamDestroy(s);
-    if (e != hipSuccess) return fail_runtime(e, "gpmi_probe_stream_overlap");
-    return GPMI_OK;
-}
-
-// The resident potrf128 server itself (panel_mfma.hip, experiment) beside a GEMM and nothing else: starts it on the context's
-// server stream with the given mode bits, times gpmi_probe_gemm's launches, stops it.  out as gpmi_probe_gemm.
-int gpmi_probe_gemm_beside_server(gpmi_ctx* c, int64_t M, int64_t N, int64_t K, int lower, int variant, int reps, int mode,
-                                  double* out) {
-    if (!c || !out) return fail_arg("gpmi_probe_gemm_beside_server: null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!c->pmail.p) {
-        HIP_TRY(c->pmail.ensure(sizeof(PotrfMail)));
-        HIP_TRY(hipMemset(c->pmail.p, 0, sizeof(PotrfMail)));
-        c->pserver.mail = c->pmail.as<PotrfMail>();
-    }
-    if (!c->sstream) {
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        HIP_TRY(hipStreamCreateWithPriority(&c->sstream, hipStreamNonBlocking, hi));
-    }
-    c->pserver.mode = mode;
-    if (mode) HIP_TRY(potrf_server_start(&c->pserver, c->sstream));
-    const int rc = gpmi_probe_gemm(c, M, N, K, lower, variant, reps, out);
-    if (mode) {
-        HIP_TRY(potrf_server_stop(&c->pserver, c->pstream));
-        HIP_TRY(hipStreamSynchronize(c->pstream));
-        HIP_TRY(hipStreamSynchronize(c->sstream));
-    }
-    return rc;
 }
 
 int gpmi_probe_hbm_write(gpmi_ctx* c, int64_t bytes, double* gbps) {

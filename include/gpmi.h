@@ -34,7 +34,7 @@ extern "C" {
 #define GPMI_ERR_BAD_ARG 2
 #define GPMI_ERR_RUNTIME 3
 
-#define GPMI_ABI_VERSION 1
+#define GPMI_ABI_VERSION 2
 
 /* stage timer slots filled by gpmi_get_timers (milliseconds, hipEvent-timed on
  * the context's compute stream; 0 when the stage did not run in the last call) */
@@ -224,12 +224,6 @@ int gpmi_probe_mfma_f64_ex(gpmi_ctx* ctx, int blocks_per_cu, int nacc, int iters
  * ablation bits (0 = the production kernel); out[0] = TFLOP/s, out[1] = ms per launch */
 int gpmi_probe_gemm(gpmi_ctx* ctx, int64_t M, int64_t N, int64_t K, int lower, int variant, int reps,
                     double* out);
-/* one resident workgroup that does nothing (threads, lds_bytes of untouched LDS), asleep for `milliseconds` on a stream of its
- * own (high_priority != 0: highest stream priority); returns at once -- time gpmi_probe_gemm while it is resident.
- * poll_sleep > 0: instead of sleeping, thread 0 re-reads a device flag with agent-scope atomic loads, s_sleep(poll_sleep)
- * between two reads (how a flag-chained resident kernel waits); fences != 0: plus an agent-scope acquire + release every ~30 us */
-int gpmi_probe_resident(gpmi_ctx* ctx, int high_priority, int lds_bytes, int threads, double milliseconds, int poll_sleep,
-                        int fences);
 /* streaming-store bandwidth (GB/s) over `bytes` of device memory */
 int gpmi_probe_hbm_write(gpmi_ctx* ctx, int64_t bytes, double* gbps);
 /* streaming bandwidth with a chosen access form: mode 0 grid-stride 16-byte stores, 1 the same
@@ -242,19 +236,6 @@ int gpmi_device_info(gpmi_ctx* ctx, double* out, int count);
  * m rows (trsm128); *out_us = microseconds per launch; stamps_out (64 entries or NULL) = in-kernel clock stamps
  * of one instrumented launch (layout: csrc/panel_mfma.hip) */
 int gpmi_probe_panel(gpmi_ctx* ctx, int kind, int64_t m, int reps, double* out_us, uint64_t* stamps_out);
-/* diagnostic: gpmi_probe_gemm while the resident potrf128 server (option potrf_server, an experiment) sits on a CU with
- * the given mode bits and is never used; 0: no server */
-int gpmi_probe_gemm_beside_server(gpmi_ctx* ctx, int64_t M, int64_t N, int64_t K, int lower, int variant, int reps, int mode,
-                                  double* out);
-/* diagnostic: n_high streams at the highest priority + n_norm at the default one, one sleeping one-wave kernel of
- * `milliseconds` on each; *wall_ms = time until all are done (about `milliseconds` when every stream has a hardware
- * queue of its own, a multiple when streams share one) */
-int gpmi_probe_stream_overlap(gpmi_ctx* ctx, int n_high, int n_norm, double milliseconds, double* wall_ms);
-/* diagnostic: `count` one-wave kernels of sleep_us microseconds each on a stream of their own (high_priority != 0: the
- * device's highest priority), back to back; kind 0 sleep only, 1 + an agent-scope release / acquire fence pair, 2 + an
- * agent-scope atomic store.  Returns at once: time gpmi_probe_gemm meanwhile to see what a second stream's kernel
- * boundaries cost a long-running GEMM. */
-int gpmi_probe_launch_storm(gpmi_ctx* ctx, int high_priority, int count, double sleep_us, int kind);
 /* diagnostic: the give-up path of the one-launch backward solve.  An n x n identity system whose bottom block is
  * deliberately never solved: every wait runs into its bound (wait_ms here, 10 s in the product), the kernel must set
  * its error word (*err_out = 1), leave NaN in the entries it waited for (x_out, n doubles) and RETURN
@@ -360,8 +341,8 @@ int gpmi_dev_trsv_lt_chain(void* stream, double* L_dev, int64_t ld, double* vsid
 /* on != 0: the block primitives called from this thread run beside a trailing update on another stream (lookahead)
  * and use their small-LDS forms, which fit on a CU next to an update workgroup; same results.  0 switches back. */
 int gpmi_dev_set_concurrent(int on);
-/* kernel-selection options (the gpmi_set_option names that choose between kernel forms: "gemm_ticket", "gemm_reserve",
- * "gemm_persist", "panel_prio", ...) for the context-free block primitives called from THIS thread; same results
+/* kernel-selection options (the gpmi_set_option names that choose between kernel forms: "gemm_ticket", "gemm_persist",
+ * "gemm_tall", ...) for the context-free block primitives called from THIS thread; same results
  * whatever the choice.  The multi-rank driver switches its large update launches to the ticket form with it. */
 int gpmi_dev_set_option(const char* name, int64_t value);
 /* f2 on device pointers, one row chunk of the gradient trace (tune_hyperparms_regression.py:43-57):

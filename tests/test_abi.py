@@ -40,6 +40,22 @@ def test_ctypes_table_covers_the_header():
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
 
 
+def test_retired_resident_experiment_options_and_probes_are_gone():
+    """the resident potrf128 server, the software CU reservation of the ticket GEMM and the probes that parked resident
+    workgroups on the chip were removed: their option names are unknown, the kernel-form options beside them still take
+    their defaults, and the probes are not exported (gpmi_dev_set_option only writes this thread's options: no device)"""
+    from gaussian_process_amd import _lib
+    lib = _lib.load()
+    for name in (b"potrf_server", b"gemm_reserve"):
+        assert lib.gpmi_dev_set_option(name, 0) == _lib.GPMI_ERR_BAD_ARG, name
+    for name, default in ((b"gemm_ticket", 0), (b"gemm_persist", 1), (b"gemm_tall", 1)):
+        assert lib.gpmi_dev_set_option(name, default) == _lib.GPMI_OK, _lib.last_error()
+    raw = C.CDLL(_lib.LIB_PATH)
+    for name in ("gpmi_probe_resident", "gpmi_probe_gemm_beside_server", "gpmi_probe_stream_overlap",
+                 "gpmi_probe_launch_storm"):
+        assert not hasattr(raw, name), name
+
+
 def test_no_silent_cpu_fallback_without_gpu():
     """Without a device the product path must fail loudly, never compute on the CPU."""
     from gaussian_process_amd import _lib

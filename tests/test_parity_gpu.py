@@ -1073,13 +1073,12 @@ def test_persistent_update_gemm_gives_the_same_bits(ctx, oracle, N, n):
     assert np.max(np.abs(out[1][1] - ref["mu"])) <= MU_ATOL
 
 
-@pytest.mark.parametrize("N,n,opts", [(9000, 300, {"gemm_ticket": 2}), (9000, 300, {"gemm_ticket": 2, "gemm_reserve": 3}),
-                                      (16384, 256, {"gemm_ticket": 1}), (16384, 256, {"gemm_ticket": 1, "gemm_reserve": 2})])
+@pytest.mark.parametrize("N,n,opts", [(9000, 300, {"gemm_ticket": 2}), (16384, 256, {"gemm_ticket": 1})])
 def test_ticket_update_gemm_gives_the_same_bits(ctx, oracle, N, n, opts):
     """the ticket form of the update GEMM (round 4: resident workgroups that draw tiles from per-XCD counters and take over
-    the other XCDs' tails, optionally leaving gemm_reserve CUs per XCD untouched) runs the per-tile kernel's code tile for
-    tile: LML, mean, variance and alpha bit for bit, with one stream (gemm_ticket 2, N below the lookahead threshold) and
-    for the Cholesky's trailing updates under lookahead (gemm_ticket 1)"""
+    the other XCDs' tails) runs the per-tile kernel's code tile for tile: LML, mean, variance and alpha bit for bit, with
+    one stream (gemm_ticket 2, N below the lookahead threshold) and for the Cholesky's trailing updates under lookahead
+    (gemm_ticket 1)"""
     X, y, Xs = oracle.synthetic_problem(N, 8, n, seed=N + n)
     out = []
     for on in (False, True):
@@ -1139,27 +1138,6 @@ def test_dev_sum_fixed_and_axpy2d_against_numpy():
     bound = np.zeros_like(want)                                           # of the operands, not of a cancelling sum
     bound[30:40, 100:104] = 2.3e-16 * (np.abs(before) + 2.5 * np.abs(X[30:40, 100:104]))
     assert np.all(np.abs(Yd.cpu().numpy() - want) <= bound)
-
-
-def test_resident_potrf_server_gives_the_same_bits(ctx, oracle):
-    """option potrf_server (round 4, an experiment kept for its measurements: LAB_NOTES.md): the 128 x 128 diagonal blocks are
-    factored by ONE resident workgroup fed through a mailbox instead of one launch each -- the same code on the same data in
-    the same order: LML, mean, variance and alpha bit for bit; the server leaves when the factorisation ends (a second fit
-    and a fit without it work afterwards)"""
-    N, n = 16384, 256
-    X, y, Xs = oracle.synthetic_problem(N, 8, n, seed=5)
-    out = []
-    for on in (0, 1, 1, 0):
-        ctx.set_option("potrf_server", on)
-        try:
-            lml = ctx.fit(X, y, 1.0, 2.0, 5e-4)
-            mu, var = ctx.predict(Xs, want_sd=False)
-            out.append((lml, mu.copy(), var.copy(), ctx.alpha()))
-        finally:
-            ctx.set_option("potrf_server", 0)
-    for o in out[1:]:
-        assert o[0] == out[0][0]
-        assert np.array_equal(o[1], out[0][1]) and np.array_equal(o[2], out[0][2]) and np.array_equal(o[3], out[0][3])
 
 
 # ---- prediction() in one pass: the test set's rows ride through the Cholesky (gpmi_fit_predict_resident) --------------
