@@ -13,6 +13,8 @@
 // One 128 x 128 tile per block, a column pair x 32 rows per thread, X tiles in LDS
 // (d <= 32) or straight from global memory; per-block partial sums, reduced in a
 // fixed order (bitwise reproducible); the host adds the per-tile partials in order.
+#include <algorithm>
+
 #include "gpmi_internal.h"
 
 namespace gpmi {
@@ -28,6 +30,7 @@ struct GradDev {
     int64_t nA, nB;
     int d;
     int64_t row0;           // first global row of this launch (index into A and alpha_r)
+    int64_t rend;           // row0 + nrows: the last tile row may reach past it, but Kinv holds nrows rows only
     int Tm, Tn;
     const double* alpha_r;  // length nA
     const double* alpha_c;  // length nB
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
     for (int r = 0; r < 32; ++r) {
         const int lr = 32 * rg + r;
         const int64_t gr = grow0 + lr;
-        if (gr >= p.nA) break;                                   // wave-uniform
+        if (gr >= p.rend) break;                                 // wave-uniform
         double s0 = 0.0, s1 = 0.0;
         if (LDS) {
             const double* ar = &As[lr * d];
@@ -154,6 +157,7 @@ hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a) {
     if (a.nrows <= 0 || a.nB <= 0) return hipSuccess;
     GradDev p;
     p.A = a.A; p.B = a.B; p.nA = a.nA; p.nB = a.nB; p.d = (int)a.d; p.row0 = a.row0;
+    p.rend = std::min(a.row0 + a.nrows, a.nA);
     p.Tm = (int)((a.nrows + RT - 1) / RT); p.Tn = (int)((a.nB + RT - 1) / RT);
     p.alpha_r = a.alpha_r; p.alpha_c = a.alpha_c;
     p.Kinv = a.Kinv; p.ld = a.ld; p.kinv_sign = a.kinv_sign;

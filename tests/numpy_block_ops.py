@@ -127,7 +127,7 @@ class NumpyBlockOps:
     def gemm_nt_rowmap(self, Cm, A, B, row_ncols, row_block_rows, row_ncols_host=None):
         c, a, b = self._a(Cm), self._a(A), self._a(B)
         nc = row_ncols.numpy()
-        for q in range(c.shape[0] // row_block_rows):
+        for q in range(-(-c.shape[0] // row_block_rows)):          # the last band may be partial
             rs = slice(q * row_block_rows, (q + 1) * row_block_rows)
             w = int(nc[q])
             w_t = min((w + 127) // 128 * 128, c.shape[1])     # the kernel works on whole 128-col tiles
@@ -136,13 +136,14 @@ class NumpyBlockOps:
     def gemm_nt_blocks(self, Cm, A, Bflat, ldb, boff, brows, row_ncols=None, row_block_rows=128, row_ncols_host=None):
         c, a = self._a(Cm), self._a(A)
         flat, K = self._a(Bflat), a.shape[1]
-        nblk = c.shape[1] // brows
+        nblk = -(-c.shape[1] // brows)              # the last block may reach past N
         b = np.vstack([flat[int(o):int(o) + brows * ldb].reshape(brows, ldb)[:, :K] for o in boff.numpy()[:nblk]])
+        b = b[:c.shape[1]]
         if row_ncols is None:
             c -= a @ b.T
             return
         nc = row_ncols.numpy()
-        for q in range(c.shape[0] // row_block_rows):
+        for q in range(-(-c.shape[0] // row_block_rows)):
             rs = slice(q * row_block_rows, (q + 1) * row_block_rows)
             w_t = min((int(nc[q]) + 127) // 128 * 128, c.shape[1])
             c[rs, :w_t] -= a[rs] @ b[:w_t].T
