@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgpmi355x.so")
 
 GPMI_OK, GPMI_ERR_NOT_PD, GPMI_ERR_BAD_ARG, GPMI_ERR_RUNTIME = 0, 1, 2, 3
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # stage-timer slots (enum in gpmi.h)
 T_KBUILD, T_CHOL, T_CHOL_PANEL, T_CHOL_TRAIL, T_LML, T_KS, T_SOLVE_V, T_MEANVAR, \
@@ -63,6 +63,8 @@ SIGNATURES = {
     "gpmi_lml_grad": [_vp, _dp, _dp],
     "gpmi_grad_trace": [_vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, _dp, _dp, _dp, _dp],
     "gpmi_lml_batch": [_vp, _dp, _i64, _dp, C.POINTER(C.c_int)],
+    "gpmi_laplace_fit": [_vp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp],
+    "gpmi_laplace_predict_resident": [_vp, _dp, _dp, _dp],
     "gpmi_get_timers": [_vp, _dp, C.c_int],
     "gpmi_sync": [_vp],
     "gpmi_probe_mfma_f64": [_vp, _dp],

@@ -72,7 +72,8 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
-                       &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside})
+                       &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
+                       &c->lap, &c->lap_part, &c->lap_out})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -130,7 +131,7 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "ld_pad")) {
         if (value < 0 || value % 2) return fail_arg("ld_pad must be even and >= 0");
         c->ld_pad = value;
-        c->have_factor = c->have_v = false;
+        c->have_factor = c->have_v = c->have_laplace = false;
     } else if (!strcmp(name, "timing")) {
         c->timing = value ? 1 : 0;
     } else if (!strcmp(name, "lookahead")) {
@@ -174,7 +175,7 @@ int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
     if (kind < 0 || kind > 2) return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear) or 2 (periodic)");
     if (kind == 2 && (!(p0 != 0.0) || !(p1 != 0.0))) return fail_arg("gpmi_set_kernel: period and lengthscale must be non-zero");
     c->kind = kind; c->kp0 = p0; c->kp1 = p1;
-    c->have_factor = c->have_v = false;
+    c->have_factor = c->have_v = c->have_laplace = false;
     return GPMI_OK;
 }
 
@@ -190,7 +191,7 @@ int gpmi_set_kernel_params(gpmi_ctx* c, int kind, const double* params, int npar
         return fail_arg("gpmi_set_kernel_params: theta_2, 4, 5, 7, 8, 10 divide and must be non-zero");
     c->kind = 3;
     for (int i = 0; i < 11; ++i) c->kpv[i] = params[i];
-    c->have_factor = c->have_v = false;
+    c->have_factor = c->have_v = c->have_laplace = false;
     return GPMI_OK;
 }
 
@@ -289,7 +290,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (!c || !X || !y) return fail_arg("gpmi_set_train: null argument");
     if (N <= 0 || d <= 0) return fail_arg("gpmi_set_train: N and d must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    c->have_train = c->have_factor = c->have_v = c->have_test = false;
+    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = false;
     HIP_TRY(c->X.ensure((size_t)N * d * 8));
     HIP_TRY(c->y.ensure((size_t)N * 8));
     HIP_TRY(hipMemcpyAsync(c->X.p, X, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream));
@@ -351,9 +352,11 @@ int gpmi_get_factor_block(gpmi_ctx* c, int64_t r0, int64_t r1, int64_t c0, int64
     return GPMI_OK;
 }
 
+}  // extern "C"
+
 // L^T x = b on the resident fused factor (a5): the first call after a factorisation inverts the 128 x 128 diagonal
 // blocks into their upper triangles (one launch, all blocks at once), every call then runs one product per block
-static hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
+hipError_t gpmi::backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
     double* A = c->A.as<double>();
     const int mode = tuning().trsv_vinv;
     if (!mode) return launch_trsv_lt_fused(c->stream, A, c->ldA, b, xout, c->Np);
@@ -372,6 +375,8 @@ static hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
     }
     return launch_trsv_lt_vinv(c->stream, A, c->ldA, b, xout, c->Np);
 }
+
+extern "C" {
 
 int gpmi_get_alpha(gpmi_ctx* c, double* alpha_out) {
     if (!c || !alpha_out) return fail_arg("gpmi_get_alpha: null argument");
@@ -834,6 +839,21 @@ int gpmi_lml_batch(gpmi_ctx* c, const double* triples, int64_t T, double* lml_ou
         for (int r = 0; r < L; ++r) c->stage_ms[i] += lane_ms[(size_t)r][(size_t)i];
     }
     return GPMI_OK;
+}
+
+// Binary GP classification, GPML Algorithms 3.1 / 3.2 with the logistic likelihood (laplace.hip)
+int gpmi_laplace_fit(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
+                     int* converged, double* f_hat) {
+    if (!c) return fail_arg("gpmi_laplace_fit: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    TuneScope tune_scope(&c->tune);
+    return laplace_fit_impl(c, sigma, ell, tol, max_iter, log_q, iters, converged, f_hat);
+}
+
+int gpmi_laplace_predict_resident(gpmi_ctx* c, double* f_mean, double* f_var, double* prob) {
+    if (!c) return fail_arg("gpmi_laplace_predict: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return laplace_predict_impl(c, f_mean, f_var, prob);
 }
 
 int gpmi_get_timers(gpmi_ctx* c, double* stage_ms, int count) {

@@ -150,6 +150,12 @@ struct gpmi_ctx {
     DevBuf cov_a, cov_b, cov_out;   // gpmi_rbf / gpmi_cov staging, kept across calls (the BO loops call them hundreds of times)
     DevBuf U, Kn, gpart;     // f2: L^-T, -(K+sI)^-1, per-tile partial sums of the gradient trace
     double sigma = 1.0, ell = 1.0;   // hyper-parameters of the resident factorisation
+    // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
+    // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
+    // A Laplace factor is not a regression factor: gpmi_laplace_fit clears have_factor, every regression factorisation
+    // (and anything else that clears have_factor) clears have_laplace.
+    bool have_laplace = false;
+    DevBuf lap, lap_part, lap_out;
     // timers
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -229,5 +235,13 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
                    bool with_test = false, double* mu = nullptr, double* out2 = nullptr, int want_sd = 1,
                    bool with_post = false, double jitter = 0.0);
 void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, double* out2, int want_sd);
+// gpmi_api.hip: L^T x = b on the resident fused factor (a5; the first call after a factorisation inverts its diagonal blocks)
+hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout);
+
+// laplace.hip: GPML Algorithms 3.1 (Newton iteration for the mode, logistic likelihood) and 3.2 (prediction)
+int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
+                     int* converged, double* f_hat);
+int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob);
+void laplace_quad_nodes(double sig2, int* M, double* T, double* h);
 
 }  // namespace gpmi

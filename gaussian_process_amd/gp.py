@@ -285,6 +285,34 @@ class GPContext:
                                         C.byref(dl), C.byref(ds)))
         return dl.value, ds.value
 
+    # ---- binary classification (Laplace approximation) --------------------------------
+    def laplace_fit(self, X, y, sigma, l, *, tol=1e-10, max_iter=100):
+        """GPML Algorithm 3.1 (logistic likelihood) on the GPU for labels y in {-1, +1} and the squared-exponential
+        kernel sigma**2 exp(-.5 sqdist / l**2).  Returns (log_q, f_hat, iters, converged): the Laplace approximation of
+        the log marginal likelihood (GPML eq. 3.32), the posterior mode, the Newton steps taken and whether
+        |Psi - Psi_prev| <= tol max(1, |Psi|) was reached (a RuntimeWarning when not).  The mode and the factor of
+        B = I + W^1/2 K W^1/2 stay on the device for laplace_predict."""
+        import warnings
+        self.set_train(X, y)
+        log_q = C.c_double()
+        iters, conv = C.c_int(), C.c_int()
+        f_hat = np.empty(self.N)
+        st = self._lib.gpmi_laplace_fit(self._h, scalar(sigma, "sigma"), scalar(l, "l"), float(tol), int(max_iter),
+                                        C.byref(log_q), C.byref(iters), C.byref(conv), ptr(f_hat))
+        check(st)
+        if not conv.value:
+            warnings.warn("Laplace approximation: Newton iteration did not converge in %d steps (tol=%g)"
+                          % (iters.value, tol), RuntimeWarning, stacklevel=2)
+        return log_q.value, f_hat, iters.value, bool(conv.value)
+
+    def laplace_predict(self, Xs):
+        """GPML Algorithm 3.2 on the resident Laplace fit: (f_mean, f_var, prob) of the latent function at Xs and
+        prob = int expit(z) N(z | f_mean, f_var) dz, the predictive probability of the label +1."""
+        self.set_test(Xs)
+        f_mean, f_var, prob = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        check(self._lib.gpmi_laplace_predict_resident(self._h, ptr(f_mean), ptr(f_var), ptr(prob)))
+        return f_mean, f_var, prob
+
     # ---- batched LML ----------------------------------------------------------------
     def lml_batch(self, triples):
         """triples: (T,3) = (l, sigma_f, noise_var) rows.  Returns (lml[T], status[T])."""

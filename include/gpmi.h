@@ -34,7 +34,7 @@ extern "C" {
 #define GPMI_ERR_BAD_ARG 2
 #define GPMI_ERR_RUNTIME 3
 
-#define GPMI_ABI_VERSION 2
+#define GPMI_ABI_VERSION 3
 
 /* stage timer slots filled by gpmi_get_timers (milliseconds, hipEvent-timed on
  * the context's compute stream; 0 when the stage did not run in the last call) */
@@ -207,6 +207,26 @@ int gpmi_grad_trace(gpmi_ctx* ctx, const double* a, const double* b, int64_t N, 
  * independent of it; the factor left resident is that of the last triple. */
 int gpmi_lml_batch(gpmi_ctx* ctx, const double* triples, int64_t T, double* lml_out,
                    int* status_out);
+
+/* Binary GP classification by the Laplace approximation: Rasmussen & Williams, GPML, Algorithm 3.1 (Newton iteration
+ * for the posterior mode, logistic likelihood) and 3.2 (prediction), with the labels +-1 of GP_binary_classification.py.
+ * On the resident training set (gpmi_set_train; y exactly -1 or +1, else GPMI_ERR_BAD_ARG), squared-exponential kernel
+ * only (a kind other than 0 -> GPMI_ERR_BAD_ARG), K = sigma^2 exp(-.5 / l^2 sqdist) without noise.  From a = f = 0 each
+ * iteration forms f = K a, pi = expit(f), W = pi (1 - pi), grad = (y + 1) / 2 - pi, b = W f + grad and the objective
+ * Psi = -a^T f / 2 + sum log p(y|f); it has converged when |Psi - Psi_prev| <= tol max(1, |Psi|), a drop of more than that
+ * halves the step (a <- (a + a_prev) / 2, at most 20 times); otherwise B = I + W^1/2 K W^1/2 is factored and
+ * a = b - W^1/2 B^-1 W^1/2 K b.  At most max_iter steps; *iters = steps taken, *converged = 0 / 1.
+ *   log_q = Psi(f^) - sum log diag(chol B(f^))          (GPML eq. 3.32 at the mode f^)
+ * f_hat: N doubles or NULL.  f^, grad(f^), W^1/2(f^) and the factor of B(f^) stay resident in place of any regression
+ * factor: gpmi_predict*, gpmi_get_alpha, gpmi_post_* and gpmi_lml_grad then refuse (GPMI_ERR_BAD_ARG) until the next
+ * regression factorisation, which in turn drops the Laplace state. */
+int gpmi_laplace_fit(gpmi_ctx* ctx, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
+                     int* converged, double* f_hat);
+/* Prediction on the resident test set (gpmi_set_test) from the resident Laplace fit (Algorithm 3.2):
+ *   f_mean = K(X*, X) grad(f^),  f_var = sigma^2 - |B^-1/2 W^1/2 K(X, X*)|^2 per test point,
+ *   prob = int expit(z) N(z | f_mean, f_var) dz     (composite trapezoid rule, error below 1e-12)
+ * each n doubles or NULL. */
+int gpmi_laplace_predict_resident(gpmi_ctx* ctx, double* f_mean, double* f_var, double* prob);
 
 int gpmi_get_timers(gpmi_ctx* ctx, double* stage_ms, int count);
 /* block the host until everything queued on the context has finished */
