@@ -7,7 +7,13 @@ One "step" = the whole hot path on inputs already resident in HBM:
 value = algorithmic fp64 flops of that path (N^3/3 + N^2/2 + N/6 for the Cholesky,
 N^2*n for the triangular solve of K_s) / wall time, whole job, in TFLOP/s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size N] [--dim d] [--ntest n] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size N] [--dim d] [--ntest n] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, seconds, ms_per_step,
+config, lml, ...).  --full also measures and checks everything beyond that figure, after the timed steps: the other call
+form, the roofline blocks and stage timers, the probed and reported peaks, the transfer-inclusive step, BASELINE configs
+2 / 5 / 4's workload at the headline size, the CPU baseline and, with --gpus N > 1, the per-rank timers and the
+self-diagnosing extra step.  --no-other-form / --no-extra-configs / --no-cpu-baseline leave pieces of --full out.
 
 --dump-outputs DIR: after the timed steps, what the last of them handed its caller -- lml, mu, var (the predictive
 variance), alpha -- is written as DIR/<name>.npy in float64.  The inputs come from a fixed seed, so two builds run with
@@ -519,6 +525,9 @@ def main():
     ap.add_argument("--size", type=int, default=65536)
     ap.add_argument("--dim", type=int, default=8)
     ap.add_argument("--ntest", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure (other call form, "
+                         "rooflines, peaks, transfers, other configs, CPU baseline, per-rank diagnosis)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-form", action="store_true",
                     help="do not time the other call form after the timed region (profiling passes: every launch of the run "
@@ -718,11 +727,12 @@ def main():
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:       # every rank holds the whole result (DistGP gathers it)
         dump_outputs(args.dump_outputs, {"lml": lml, "mu": mu, "var": var, "alpha": alpha})
-    per_rank = None
+    per_rank, diag_all = None, None
     if multi:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if multi and args.full:
         stage = timers_fn()
         mine = torch.tensor([stage.get("fit", 0.0), stage.get("alpha", 0.0), stage.get("predict", 0.0)],
                             device="cuda", dtype=torch.float64)
@@ -736,7 +746,6 @@ def main():
         # step.  A sub-target scaling number can then be read: compute (update_ms against 1/world of the single-GPU
         # update time), exposed communication (stall_panel_ms), or a host that cannot issue fast enough (host_issue_ms
         # against the step's wall).
-        diag_all = None
         if os.environ.get("GPMI_BENCH_NO_DIAG") != "1":
             gp.profile(True)
             barrier()
@@ -756,7 +765,7 @@ def main():
     flops = algorithmic_flops(N, n)
     value = flops / (dt / args.steps) / 1e12
     other_form = None
-    if not multi and not args.no_other_form:
+    if not multi and args.full and not args.no_other_form:
         # the other call form, outside the timed region: its wall, its results against the timed form's, and -- from the
         # two-call form, where a7 runs alone -- the stage timers of the predict sweep
         other = step_two if one_pass else step_one
@@ -798,7 +807,8 @@ def main():
             out["config"]["call_form"] = ("one pass: gpmi_fit_predict_resident (K build, Cholesky with the test set's rows "
                                           "K(X*, X) carried along = a7, LML, mean, variance) + gpmi_get_alpha" if one_pass
                                           else "two calls: gpmi_factorize + gpmi_get_alpha + gpmi_predict_resident")
-            out["other_call_form"] = other_form
+            if args.full:
+                out["other_call_form"] = other_form
         targets = {}
         if multi:
             out["rccl_ranks"] = dist.get_world_size()
@@ -809,21 +819,22 @@ def main():
                                           "its row blocks; no message of their own) + alpha" if dist_one_pass
                                           else "two calls: factorize + alpha + predict_resident")
             out["config"]["update_form"] = update_form if update_form is not None else ("ticket" if gp.ticket else "per-tile")
-            out["stages_ms"] = stage            # last step, rank 0: fit / alpha / predict wall
-            out["per_rank_ms"] = per_rank
-            out["per_rank_diag"] = diag_all
-            out["per_rank_diag_note"] = ("one extra step outside the timed region, events on the stream each piece runs on: "
-                                         "update = trailing-update launches of the fit, allgather / bcast / pack = panel "
-                                         "collectives and the pack copy, stall_panel = main stream waiting for the panel "
-                                         "chain, diag / panel_solve = diagonal-block factorisations and panel solves, "
-                                         "*_v = predict sweep, alpha_* = backward solve, host_issue = host time to issue "
-                                         "each fit step")
+            if args.full:
+                out["stages_ms"] = stage            # last step, rank 0: fit / alpha / predict wall
+                out["per_rank_ms"] = per_rank
+                out["per_rank_diag"] = diag_all
+                out["per_rank_diag_note"] = ("one extra step outside the timed region, events on the stream each piece runs "
+                                             "on: update = trailing-update launches of the fit, allgather / bcast / pack = "
+                                             "panel collectives and the pack copy, stall_panel = main stream waiting for the "
+                                             "panel chain, diag / panel_solve = diagonal-block factorisations and panel "
+                                             "solves, *_v = predict sweep, alpha_* = backward solve, host_issue = host time "
+                                             "to issue each fit step")
             out["comm"] = gp.comm.describe()
             if force_dist:
                 out["config"]["partition"] = "multi-rank driver forced on one rank (RCCL communicator of size 1)"
             targets["speedup_8gpu"] = {"target": TARGET_SPEEDUP_8, "note": "value at n_gpus=8 / value at n_gpus=1; "
                                        "computed by the driver from the per-N lines"}
-        if not multi and stage:
+        if args.full and not multi and stage:
             k = args.steps
             trail_ms = stage.get("chol_trail", 0.0) / k
             trail_flops = stage.get("trail_flops", 0.0) / k
@@ -927,8 +938,9 @@ def main():
                             "nominal 8 TB/s (8192 bits x 8 Gb/s per pin)"}
             except Exception as e:      # never cost the bench line
                 out["peaks_box"] = {"error": str(e)}
-        out["targets"] = targets
-        if not multi:
+        if args.full:
+            out["targets"] = targets
+        if args.full and not multi:
             # the wall "including H2D of X, y, Xs and D2H of mu, sigma" -- one step timed around
             # the uploads as well (gpmi_set_train + gpmi_set_test: H2D copies, bounding boxes on the host); never `value`
             wd.beat("step incl. transfers")
@@ -950,7 +962,7 @@ def main():
                     out["extra_configs"] = {"error": repr(e)}
         wd.beat("cpu baseline")
         wd.stall_s = max(wd.stall_s, 600.0)       # CPU work: no heartbeat inside
-        if world == 1 and not args.no_cpu_baseline and not force_dist:
+        if world == 1 and args.full and not args.no_cpu_baseline and not force_dist:
             out["cpu_baseline"] = cpu_baseline(d, n)
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)

@@ -16,25 +16,25 @@ timeout -k 10 600 python3 -m pytest tests/test_dist.py -x -q -m gpu -k "two_rank
 tail -3 $OUT/1_pytest.txt
 
 say "2/4 bench.py --gpus 2 at N=16384 (one step)"
-timeout -k 10 400 python3 bench.py --gpus 2 --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/2_bench_g2.json 2> $OUT/2_bench_g2.err \
+timeout -k 10 400 python3 bench.py --full --gpus 2 --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/2_bench_g2.json 2> $OUT/2_bench_g2.err \
     || { say "FAILED at stage 2 (see $OUT/2_bench_g2.err: the last '[bench] rank r step k phase' lines name the collective)"; tail -30 $OUT/2_bench_g2.err; exit 2; }
 cut -c1-300 $OUT/2_bench_g2.json
 
 say "3/4 bench.py --gpus $NG at N=16384 (one step)"
-timeout -k 10 400 python3 bench.py --gpus $NG --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/3_bench_gN_small.json 2> $OUT/3_bench_gN_small.err \
+timeout -k 10 400 python3 bench.py --full --gpus $NG --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/3_bench_gN_small.json 2> $OUT/3_bench_gN_small.err \
     || { say "FAILED at stage 3 (see $OUT/3_bench_gN_small.err)"; tail -40 $OUT/3_bench_gN_small.err; exit 3; }
 cut -c1-300 $OUT/3_bench_gN_small.json
 
 say "3b/4 the same through this library's own RCCL binding (GPMI_DIST_COMM=rccl; not fatal: the line above is the default path)"
-GPMI_DIST_COMM=rccl timeout -k 10 400 python3 bench.py --gpus $NG --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/3b_bench_gN_small_cabi.json 2> $OUT/3b_bench_gN_small_cabi.err \
+GPMI_DIST_COMM=rccl timeout -k 10 400 python3 bench.py --full --gpus $NG --size 16384 --ntest 1024 --steps 1 --warmup 0 > $OUT/3b_bench_gN_small_cabi.json 2> $OUT/3b_bench_gN_small_cabi.err \
     && cut -c1-300 $OUT/3b_bench_gN_small_cabi.json || { say "stage 3b failed (see $OUT/3b_bench_gN_small_cabi.err); continuing with the default backend"; tail -20 $OUT/3b_bench_gN_small_cabi.err; }
 
 say "4/4 the real line: bench.py --gpus $NG (N=65536)"
-timeout -k 10 560 python3 bench.py --gpus $NG --steps 3 --warmup 1 > $OUT/4_bench_gN.json 2> $OUT/4_bench_gN.err \
+timeout -k 10 560 python3 bench.py --full --gpus $NG --steps 3 --warmup 1 > $OUT/4_bench_gN.json 2> $OUT/4_bench_gN.err \
     || { say "FAILED at stage 4 (see $OUT/4_bench_gN.err)"; tail -40 $OUT/4_bench_gN.err; exit 4; }
 cut -c1-400 $OUT/4_bench_gN.json
-GPMI_DIST_COMM=rccl timeout -k 10 560 python3 bench.py --gpus $NG --steps 3 --warmup 1 > $OUT/4b_bench_gN_cabi.json 2> $OUT/4b_bench_gN_cabi.err \
+GPMI_DIST_COMM=rccl timeout -k 10 560 python3 bench.py --full --gpus $NG --steps 3 --warmup 1 > $OUT/4b_bench_gN_cabi.json 2> $OUT/4b_bench_gN_cabi.err \
     && cut -c1-400 $OUT/4b_bench_gN_cabi.json || say "the C-ABI backend at full size failed (see $OUT/4b_bench_gN_cabi.err)"
-GPMI_BENCH_TWO_CALLS=1 timeout -k 10 560 python3 bench.py --gpus $NG --steps 3 --warmup 1 > $OUT/4c_bench_gN_two_calls.json 2> $OUT/4c_bench_gN_two_calls.err \
+GPMI_BENCH_TWO_CALLS=1 timeout -k 10 560 python3 bench.py --full --gpus $NG --steps 3 --warmup 1 > $OUT/4c_bench_gN_two_calls.json 2> $OUT/4c_bench_gN_two_calls.err \
     && cut -c1-400 $OUT/4c_bench_gN_two_calls.json || say "the two-call step (A/B of the one-pass step; column-wise predict with its n x nb broadcasts) failed (see $OUT/4c_bench_gN_two_calls.err)"
 say "all four stages passed"

@@ -1,4 +1,5 @@
-"""bench.py's command line: --steps, and --dump-outputs (what the last timed step handed its caller, as .npy files)."""
+"""bench.py's command line: --steps, --dump-outputs (what the last timed step handed its caller, as .npy files), and --full
+(everything the benchmark measures beyond its headline figure)."""
 import json
 import os
 import subprocess
@@ -18,9 +19,20 @@ def _bench(args, timeout):
                           text=True, timeout=timeout)
 
 
+# keys of the single-GPU line that only --full adds
+FULL_ONLY = ("other_call_form", "roofline", "stages_ms", "kbuild_hbm", "alpha_hbm", "peaks_probe", "peaks_box", "targets",
+             "seconds_incl_transfers")
+
+
 def test_bench_rejects_no_timed_steps_cpu():
     p = _bench(["--steps", "0"], timeout=60)
     assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_bench_knows_full_cpu():
+    """--full is an option of its own (the command line is parsed before anything needs a GPU)"""
+    p = _bench(["--full", "--steps", "0"], timeout=60)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr and "unrecognized" not in p.stderr
 
 
 def test_dump_outputs_bound_and_sample_cpu(tmp_path, monkeypatch):
@@ -66,3 +78,31 @@ def test_bench_dump_outputs_are_the_timed_step_results(tmp_path, oracle):
     assert np.max(np.abs(got["var"] - ref["var"])) < 1e-10
     assert abs(float(got["lml"]) - ref["lml"]) < 1e-10 * abs(ref["lml"])
     assert np.max(np.abs(got["alpha"] - ref["alpha"])) < 1e-8 * np.max(np.abs(ref["alpha"]))
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_rest(tmp_path):
+    """a plain run prints the headline line alone; --full prints the same headline with what the benchmark measures
+    beyond it, and the timed steps hand back the same bits either way"""
+    args = ["--gpus", "1", "--size", "2048", "--dim", "8", "--ntest", "128", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for form, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        p = _bench(args + extra + ["--dump-outputs", str(tmp_path / form)], timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, p.stdout[-2000:]
+        lines[form] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "seconds", "steps", "warmup",
+                    "config", "lml"):
+            assert key in line, key
+        assert line["unit"] == "TFLOP/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert plain["metric"] == full["metric"] and plain["config"]["call_form"] == full["config"]["call_form"]
+    assert not set(plain) & set(FULL_ONLY + ("cpu_baseline", "extra_configs")), sorted(plain)
+    assert set(FULL_ONLY) <= set(full), sorted(full)
+    assert full["other_call_form"]["lml_equal"] and full["other_call_form"]["alpha_equal"]
+    assert plain["lml"] == full["lml"]
+    for k in ("lml", "mu", "var", "alpha"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (k + ".npy")), np.load(tmp_path / "full" / (k + ".npy"))), k

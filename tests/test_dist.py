@@ -448,8 +448,8 @@ def test_bench_two_ranks_through_the_self_spawn_path():
     """The driver's multi-GPU command line, rehearsed on the one GPU of the test box: gloo moves the panels, both
     ranks share device 0.  One JSON line from rank 0 with n_gpus = rccl_ranks = 2."""
     import json
-    p = _bench(["--gpus", "2", "--size", "8192", "--ntest", "512", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
-               {"GPMI_BENCH_BACKEND": "gloo", "GPMI_BENCH_ONE_DEVICE": "1"})
+    p = _bench(["--gpus", "2", "--size", "8192", "--ntest", "512", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+                "--full"], {"GPMI_BENCH_BACKEND": "gloo", "GPMI_BENCH_ONE_DEVICE": "1"})
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -459,7 +459,8 @@ def test_bench_two_ranks_through_the_self_spawn_path():
     # the same problem on the single-GPU path: the same log-marginal-likelihood to the path's LML tolerance (the two
     # factorisations block differently -- 512 rows per block here, 512-column panels there -- and the LML is a sum of
     # cancelling terms a hundred times its size: 4e-12 relative measured)
-    p1 = _bench(["--gpus", "1", "--size", "8192", "--ntest", "512", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], {})
+    p1 = _bench(["--gpus", "1", "--size", "8192", "--ntest", "512", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+                 "--full"], {})
     assert p1.returncode == 0, p1.stderr[-3000:]
     one = json.loads([l for l in p1.stdout.splitlines() if l.startswith("{")][0])
     assert abs(one["lml"] - out["lml"]) <= 1e-10 * abs(one["lml"])
