@@ -244,9 +244,11 @@ int gpmi_dev_trsv_lt_chain(void* stream, double* L_dev, int64_t ld, double* vsid
 // ring for small GEMMs), which fit on a CU next to an update workgroup and start at once.  Results are the
 // same bits either way.  0 switches back.
 int gpmi_dev_set_concurrent(int on) {
-    static thread_local GemmShallowScope* scope = nullptr;
-    if (on && !scope) scope = new GemmShallowScope(true);
-    if (!on && scope) { delete scope; scope = nullptr; }
+    static thread_local bool active = false;
+    static thread_local Sharing before;
+    if (on && !active) { before = sharing(); sharing() = Sharing::beside_update(); }
+    if (!on && active) sharing() = before;
+    active = on != 0;
     return GPMI_OK;
 }
 

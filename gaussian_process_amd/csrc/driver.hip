@@ -127,7 +127,7 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
     // panel kernels beside the trailing update use their small-LDS forms -- while there IS a trailing update of some length
     // to run beside: once the columns right of the panel are fewer than c->shallow_min, part (b) of a step is over long
     // before the panel chain is, and the one-launch forms (which then find empty CUs) are the shorter chain
-    GemmShallowScope shallow(la || follow != nullptr);
+    SharingScope shallow((la || follow) ? Sharing::beside_update() : sharing());
     // (a) on the panel stream pays at mid sizes (N = 16384: -4 %, 32768: -1 %), where a launch's tail and the
     // panel chain are a visible share of a step; at the headline size it is worth 0.4 % and would put two
     // trailing-update launches in flight at once, which makes "time per launch" (the roofline figure) ambiguous
@@ -150,9 +150,10 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         g.role = counted ? 1 : 0;
         // the roofline figures are those of the LDS-DMA kernel: the last, small updates that
         // run on the first-generation kernel are timed into the scratch slot
-        const bool dma = gemm_nt_routes_dma(g);
+        const GemmRoute route = gemm_nt_route(g);
+        const bool dma = gemm_kernel_is_dma(route.kernel);
         size_t sp = c->span_begin(counted ? (dma ? slot_t : GPMI_T_COUNT - 1) : slot_p, st);
-        hipError_t er = launch_gemm_nt(st, g);
+        hipError_t er = launch_gemm_nt(st, g, route);
         c->span_end(sp, st);
         if (account && dma && counted) {
             c->stage_ms[GPMI_T_TRAIL_LAUNCHES] += 1.0;
@@ -168,7 +169,8 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         const int64_t nb = widths[step];
         size_t sp = c->span_begin(slot_p, sp_);
         {
-            GemmShallowScope panel_forms(la && ncols - k >= c->shallow_min, la, true);
+            SharingScope panel_forms(!la ? sharing().large_lds()
+                                     : ncols - k >= c->shallow_min ? Sharing::beside_update() : Sharing::chip_shared_only());
             e = panel_factor(sp_, A + k * ld + k, ld, nb, nrows - k, k, info);
         }
         c->span_end(sp, sp_);
@@ -181,7 +183,7 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
             if ((e = c->order(sp_, follow->vs)) != hipSuccess) return e;
             {
                 // as in solve_sweep: the small-LDS solve forms only for enough rows to matter beside the updates
-                GemmShallowScope solve_forms(follow->m >= 2048, true, true);
+                SharingScope solve_forms(follow->m >= 2048 ? Sharing::beside_update() : Sharing::chip_shared_only());
                 if ((e = trsm_block(follow->vs, A + k * ld + k, ld, follow->V + k, follow->ldv, follow->m, nb)) != hipSuccess) return e;
             }
             if (r0 < ncols) {
@@ -422,7 +424,7 @@ hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri)
     // small-LDS panel forms beside the update only for sweeps with enough rows to keep the chip busy: for a few
     // hundred test points the chain of launches is what counts, and the one-launch trsm128 is shorter
     // (N = 16384, n = 1024: 7.96 against 8.47 ms)
-    GemmShallowScope shallow(la && m >= 2048, la);
+    SharingScope shallow(!la ? sharing() : m >= 2048 ? Sharing::beside_update() : sharing().and_chip_shared());
     if (la && (e = c->order(sm, sp_)) != hipSuccess) return e;
     auto update = [&](int64_t c0, int64_t k, int64_t nb, int64_t ncol_upd) -> hipError_t {
         GemmArgs g;   // V[:, c0..c0+ncol_upd) -= V[:, k..k+nb) * L[c0.., k..k+nb)^T

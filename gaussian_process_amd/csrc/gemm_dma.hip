@@ -694,7 +694,7 @@ __global__ __launch_bounds__(512, 3) void chol_trailing_update_ticket_kernel(con
 // starts over with a prologue.  vmcnt bookkeeping: the memory counter retires in order, so a wait for "the DMA of
 // step c + 1" also waits for everything issued before it -- the C loads sit between the DMA of steps nch - 1 and
 // nch, which gives them two K steps to land.
-// Used for launches that have the chip to themselves (see launch_gemm_nt_dma): at 216 registers per lane and two waves per
+// Used for launches that have the chip to themselves (gpmi_route.h: gemm_route): at 216 registers per lane and two waves per
 // SIMD nothing else fits on a CU beside a resident workgroup.  ROLE only separates the two kernel symbols.
 // ---------------------------------------------------------------------------
 template <int ROLE>
@@ -974,22 +974,13 @@ __global__ __launch_bounds__(512, 2) void chol_trailing_update_persist_kernel(co
 // K = 128 is one memory round trip, deeper K keeps seven steps in flight.  One barrier per K step: it publishes
 // step c (every wave has waited for its own pieces) and frees the stage of step c - 1 for step c + 7.
 // ---------------------------------------------------------------------------
-// Ring depth: 8 stages (128 KiB) when the launch has the chip to itself; 3 stages (48 KiB) while a trailing
+// Ring depth (gpmi_route.h: Sharing::small_lds): 8 stages (128 KiB) when the launch has the chip to itself; 3 stages (48 KiB) while a trailing
 // update runs on the other stream (lookahead) -- its workgroups hold 96 KiB of every CU's 160 KiB of LDS, and a
 // panel kernel that does not fit beside them waits for a whole tile (~130 us) instead of starting at once
 // (kernel trace: 127 us per launch with the deep ring against 65 us for the 16 KiB first-generation kernel).
 constexpr int SM_T = 64;                                   // tile edge
 constexpr int SM_STAGE_SLOTS = (SM_T + SM_T) * 8;          // 16-byte slots per stage (A then B): 16 KiB
-static thread_local int t_small_shallow = 0;
-static thread_local int t_two_streams = 0;
-GemmShallowScope::GemmShallowScope(bool on, bool two_streams, bool exact) : prev(t_small_shallow), prev_two(t_two_streams) {
-    if (on) t_small_shallow = 1;
-    else if (exact) t_small_shallow = 0;
-    if (on || two_streams) t_two_streams = 1;
-}
-GemmShallowScope::~GemmShallowScope() { t_small_shallow = prev; t_two_streams = prev_two; }
-bool gemm_shallow_active() { return t_small_shallow != 0; }
-bool gemm_two_streams_active() { return t_two_streams != 0; }
+static_assert((size_t)SM_STAGE_SLOTS * 16 == GEMM_SMALL_STAGE, "gpmi_route.h sizes the ring of a small launch");
 
 struct GemmSmallDev {
     double* C;
@@ -1097,23 +1088,18 @@ __global__ __launch_bounds__(256) void gemm_nt_small_kernel(const GemmSmallDev p
             for (int v = 0; v < 4; ++v) *c_ptr(i, j, v) = cv[i][j][v] - acc[i][j][v];
 }
 
-bool gemm_small_eligible(const GemmArgs& a) {
-    return a.mode == 0 && a.M % SM_T == 0 && a.N % SM_T == 0 && a.K % 16 == 0 && a.K >= 16 && !a.row_ncols && !a.b_block_off;
-}
-
-hipError_t launch_gemm_nt_small(hipStream_t s, const GemmArgs& a) {
+hipError_t launch_gemm_nt_small(hipStream_t s, const GemmArgs& a, const GemmRoute& r) {
     GemmSmallDev p;
     p.C = a.C; p.A = a.A; p.B = a.B; p.ldc = a.ldc; p.lda = a.lda; p.ldb = a.ldb;
     p.Tm = (int)(a.M / SM_T); p.Tn = (int)(a.N / SM_T); p.nchunks = (int)(a.K / 16);
     p.lower = a.lower; p.diag_off = a.diag_off;
-    constexpr size_t lds8 = (size_t)8 * SM_STAGE_SLOTS * 16, lds3 = (size_t)3 * SM_STAGE_SLOTS * 16;
     static PerDeviceOnce once;
     const hipError_t ea = once.run([&]() -> hipError_t {
-        return hipFuncSetAttribute((const void*)gemm_nt_small_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
+        return hipFuncSetAttribute((const void*)gemm_nt_small_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * GEMM_SMALL_STAGE));
     });
     if (ea != hipSuccess) return ea;
-    if (t_small_shallow) hipLaunchKernelGGL(gemm_nt_small_kernel<3>, dim3((unsigned)(p.Tm * p.Tn)), dim3(256), lds3, s, p);
-    else hipLaunchKernelGGL(gemm_nt_small_kernel<8>, dim3((unsigned)(p.Tm * p.Tn)), dim3(256), lds8, s, p);
+    if (r.kernel == GemmKernel::Small3) hipLaunchKernelGGL(gemm_nt_small_kernel<3>, dim3(r.grid), dim3(256), r.lds, s, p);
+    else hipLaunchKernelGGL(gemm_nt_small_kernel<8>, dim3(r.grid), dim3(256), r.lds, s, p);
     return hipGetLastError();
 }
 
@@ -1153,115 +1139,65 @@ static PersistPool* persist_pool() {
     return &pl;
 }
 
-bool gemm_dma_eligible(const GemmArgs& a) {
-    return a.mode == 0 && a.N % 128 == 0 && a.M % 128 == 0 && a.K % 16 == 0 && a.K >= 32;
+int gemm_resident_groups() {
+    const PersistPool* pool = persist_pool();
+    return pool ? pool->groups : 0;
 }
 
-hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a) {
+static_assert((size_t)DMA_STAGES * DMA_STAGE_SLOTS * 16 == GEMM_DMA_LDS && TALL_LDS == GEMM_TALL_LDS && TALL_LDS == GEMM_DMA_LDS,
+              "gpmi_route.h sizes the rings of the launches; one opt-in size serves both forms");
+
+hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a, const GemmRoute& r) {
+    const TilePlan& plan = r.plan;
     GemmDmaDev p;
     p.C = a.C; p.A = a.A; p.B = a.B;
     p.ldc = a.ldc; p.lda = a.lda; p.ldb = a.ldb;
-    p.Tm = (int)(a.M / 128); p.Tn = (int)(a.N / 128);
+    p.Tm = plan.Tm; p.Tn = plan.Tn;
     p.nchunks = (int)(a.K / 16);
     p.lower = a.lower; p.diag_off = a.diag_off;
-    p.row_ncols = a.row_ncols; p.row_block_tiles = a.row_block_tiles > 0 ? a.row_block_tiles : 1;
+    p.row_ncols = a.row_ncols; p.row_block_tiles = plan.row_block_tiles;
     p.b_block_off = a.b_block_off;
     p.b_block_tiles = a.b_block_off ? (int)(a.b_block_rows / 128) : 1;
-    if (a.b_block_off && (a.b_block_rows <= 0 || a.b_block_rows % 128)) return hipErrorInvalidValue;
-    const Tuning& tn = tuning();
-    TilePlan plan;
-    // the launch geometry: first as a resident form wants it (widest supertiles), which also decides whether one is used
-    if (!plan_tiles(plan, p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols != nullptr, a.row_ncols_host, a.row_bands,
-                    p.row_block_tiles, 0, false))
-        return hipErrorInvalidValue;
-    if (plan.nsuper == 0) return hipSuccess;
-    const bool eight = tn.gemm_dma_waves == 8 && !(tn.gemm_dbg & 0xff);
-    const bool want_ticket = eight && (tn.gemm_ticket >= 2 || (tn.gemm_ticket == 1 && a.role == 1 && gemm_two_streams_active()));
-    const bool want_persist = eight && tn.gemm_persist && a.K >= 256 && !gemm_two_streams_active();
-    PersistPool* pool = (want_ticket || want_persist) ? persist_pool() : nullptr;
-    const bool ticket = want_ticket && pool && plan.nblocks >= pool->groups;
-    const bool persist = !ticket && want_persist && pool && plan.nblocks >= 2 * pool->groups;
-    // one workgroup per tile: the supertile edge is chosen with the static deal of blocks to the XCDs in mind
-    if (!ticket && !persist &&
-        !plan_tiles(plan, p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols != nullptr, a.row_ncols_host, a.row_bands,
-                    p.row_block_tiles, 0, tn.gemm_balance != 0))
-        return hipErrorInvalidValue;
     p.S = plan.S; p.logS = plan.logS; p.SM = plan.SM; p.SN = plan.SN; p.tri = plan.tri; p.nsuper = plan.nsuper;
-    p.pair = 0;
+    p.pair = plan.pair;
     if (plan.tri == 2) std::copy(plan.sprefix, plan.sprefix + plan.SM + 1, p.sprefix);
-    const int nblocks = plan.nblocks;
-    constexpr size_t lds = (size_t)DMA_STAGES * DMA_STAGE_SLOTS * 16;
-    static PerDeviceOnce once;
+    p.dbg = tuning().gemm_dbg & 0xff;
+    p.stamps = tuning().gemm_stamps;
+    p.slot = nullptr;
+    p.nblocks = plan.nblocks;
+    static PerDeviceOnce once;      // the per-tile forms; the resident forms' opt-in is the counter pool's (persist_pool)
     const hipError_t ea = once.run([&]() -> hipError_t {
         const void* fns[] = {(const void*)gemm_nt_dma_kernel<4, false>, (const void*)gemm_nt_dma_kernel<4, true>,
                              (const void*)gemm_nt_dma_kernel<2, false>, (const void*)gemm_nt_dma_kernel<2, true>,
-                             (const void*)chol_trailing_update_dma_kernel};
+                             (const void*)chol_trailing_update_dma_kernel, (const void*)gemm_nt_dma_tall_kernel<false>,
+                             (const void*)gemm_nt_dma_tall_kernel<true>, (const void*)chol_trailing_update_dma256_kernel};
         for (const void* f : fns) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEMM_DMA_LDS);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     });
     if (ea != hipSuccess) return ea;
-    p.dbg = tn.gemm_dbg & 0xff;
-    p.stamps = tn.gemm_stamps;
-    p.slot = nullptr;
-    p.nblocks = nblocks;
-    // ticket form (option gemm_ticket: 1 for the Cholesky's trailing updates while two streams are busy, 2 for every
-    // launch of at least one round)
-    if (ticket) {
+    if (r.kernel >= GemmKernel::Persist) {          // resident forms: the launch's counters
+        PersistPool* pool = persist_pool();
+        if (!pool) return hipErrorInvalidValue;     // the route was made with this pool's group count
         p.slot = pool->next();
-        constexpr size_t ldst = lds + 16;          // ring + mailbox
-        if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_ticket_kernel, dim3(pool->groups), dim3(512), ldst, s, p);
-        else hipLaunchKernelGGL(gemm_nt_dma_ticket_kernel, dim3(pool->groups), dim3(512), ldst, s, p);
-        return hipGetLastError();
     }
-    // persistent form: launches with at least two rounds of tiles and a K loop long enough to draw the successor in --
-    // and the chip to themselves: resident workgroups (216 registers per lane, two waves per SIMD) leave no room on a
-    // CU for the panel kernels of the other stream, which would then wait for the whole launch instead of a tile
-    // (lookahead with both forms: N = 16384 fit + predict 39.8 against 42.9 ms).  No pool (its allocation or the opt-in
-    // failed, or an unusual device): the per-tile launch below computes the same bits.
-    if (persist) {
-        p.slot = pool->next();
-        constexpr size_t ldsp = lds + 16;          // ring + mailbox
-        if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_persist_kernel, dim3(pool->groups), dim3(512), ldsp, s, p);
-        else hipLaunchKernelGGL(gemm_nt_dma_persist_kernel, dim3(pool->groups), dim3(512), ldsp, s, p);
-        return hipGetLastError();
-    }
-    // tall form (option gemm_tall): 256 x 128 blocks for launches of at least tall_min_tiles live tiles, as a pair plan
-    // with the same supertiles; its own kernel symbol for the trailing updates
-    if (tn.gemm_dma_waves == 8 && tn.gemm_tall &&
-        plan_live_tiles(p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols_host, a.row_bands, p.row_block_tiles) >= tn.tall_min_tiles) {
-        TilePlan pp;
-        if (!plan_tiles(pp, p.Tm, p.Tn, a.lower, a.diag_off, a.row_ncols != nullptr, a.row_ncols_host, a.row_bands,
-                        p.row_block_tiles, 0, tn.gemm_balance != 0, true))
-            return hipErrorInvalidValue;
-        p.S = pp.S; p.logS = pp.logS; p.SM = pp.SM; p.SN = pp.SN; p.tri = pp.tri; p.nsuper = pp.nsuper; p.pair = 1;
-        if (pp.tri == 2) std::copy(pp.sprefix, pp.sprefix + pp.SM + 1, p.sprefix);
-        p.nblocks = pp.nblocks;
-        static PerDeviceOnce once_tall;
-        const hipError_t et = once_tall.run([&]() -> hipError_t {
-            const void* fns[] = {(const void*)gemm_nt_dma_tall_kernel<false>, (const void*)gemm_nt_dma_tall_kernel<true>,
-                                 (const void*)chol_trailing_update_dma256_kernel};
-            for (const void* f : fns) {
-                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TALL_LDS);
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        });
-        if (et != hipSuccess) return et;
-        if (p.dbg) hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<true>, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
-        else if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_dma256_kernel, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
-        else hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<false>, dim3(pp.nblocks), dim3(512), TALL_LDS, s, p);
-        return hipGetLastError();
-    }
-    if (tn.gemm_dma_waves == 8) {
-        if (p.dbg) hipLaunchKernelGGL((gemm_nt_dma_kernel<2, true>), dim3(nblocks), dim3(512), lds, s, p);
-        else if (a.role == 1) hipLaunchKernelGGL(chol_trailing_update_dma_kernel, dim3(nblocks), dim3(512), lds, s, p);
-        else hipLaunchKernelGGL((gemm_nt_dma_kernel<2, false>), dim3(nblocks), dim3(512), lds, s, p);
-    } else {
-        if (p.dbg) hipLaunchKernelGGL((gemm_nt_dma_kernel<4, true>), dim3(nblocks), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL((gemm_nt_dma_kernel<4, false>), dim3(nblocks), dim3(256), lds, s, p);
+    const dim3 grid(r.grid);
+    switch (r.kernel) {
+        case GemmKernel::Ticket: hipLaunchKernelGGL(gemm_nt_dma_ticket_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::TicketTrail: hipLaunchKernelGGL(chol_trailing_update_ticket_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Persist: hipLaunchKernelGGL(gemm_nt_dma_persist_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::PersistTrail: hipLaunchKernelGGL(chol_trailing_update_persist_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Tall: hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<false>, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::TallProbe: hipLaunchKernelGGL(gemm_nt_dma_tall_kernel<true>, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::TallTrail: hipLaunchKernelGGL(chol_trailing_update_dma256_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Dma8: hipLaunchKernelGGL((gemm_nt_dma_kernel<2, false>), grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Dma8Probe: hipLaunchKernelGGL((gemm_nt_dma_kernel<2, true>), grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Dma8Trail: hipLaunchKernelGGL(chol_trailing_update_dma_kernel, grid, dim3(512), r.lds, s, p); break;
+        case GemmKernel::Dma4: hipLaunchKernelGGL((gemm_nt_dma_kernel<4, false>), grid, dim3(256), r.lds, s, p); break;
+        case GemmKernel::Dma4Probe: hipLaunchKernelGGL((gemm_nt_dma_kernel<4, true>), grid, dim3(256), r.lds, s, p); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -257,48 +257,60 @@ static void plan(const GemmArgs& a, int TM, int TN, GemmDev& p, int& nblocks) {
     p.dbg = tuning().gemm_dbg;
 }
 
-bool gemm_nt_routes_dma(const GemmArgs& a) {
-    // ablation bits >= 256 select the DMA kernel's ablations (low byte passed on)
-    const Tuning& tn = tuning();
-    if (a.b_block_off) return true;            // only the LDS-DMA kernel reads B through a block table
-    return tn.gemm_use_dma && (!tn.gemm_dbg || tn.gemm_dbg >= 256) && gemm_dma_eligible(a) &&
-           (a.M / 128) * (a.N / 128) >= 128;      // from half a round of tiles up (below: 64 x 64 tiles, launch_gemm_nt_small)
+GemmRoute gemm_nt_route(const GemmArgs& a) {
+    GemmRouteIn in;
+    in.M = a.M; in.N = a.N; in.K = a.K;
+    in.mode = a.mode; in.lower = a.lower; in.diag_off = a.diag_off;
+    in.has_row_map = a.row_ncols != nullptr; in.row_ncols_host = a.row_ncols_host; in.row_bands = a.row_bands;
+    in.row_block_tiles = a.row_block_tiles;
+    in.b_blocks = a.b_block_off != nullptr; in.b_block_rows = a.b_block_rows;
+    in.role = a.role;
+    in.tune = tuning();
+    in.sharing = sharing();
+    in.groups = GROUPS_NOT_ASKED;
+    GemmRoute r;
+    gemm_route(in, r);
+    if (r.asks_groups) {
+        in.groups = gemm_resident_groups();
+        gemm_route(in, r);
+    }
+    return r;
 }
 
-hipError_t launch_gemm_nt(hipStream_t s, const GemmArgs& a) {
-    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return hipSuccess;
-    if (a.M % 128 || a.N % 64 || a.K % BK) return hipErrorInvalidValue;
-    if (a.b_block_off && !gemm_dma_eligible(a)) return hipErrorInvalidValue;
-    if (gemm_nt_routes_dma(a)) return launch_gemm_nt_dma(s, a);
-    GemmDev p;
-    int nblocks;
+hipError_t launch_gemm_nt(hipStream_t s, const GemmArgs& a, const GemmRoute& r) {
+    if (r.kernel == GemmKernel::Nothing) return hipSuccess;
+    if (r.kernel == GemmKernel::Invalid) return hipErrorInvalidValue;
+    if (gemm_kernel_is_dma(r.kernel)) return launch_gemm_nt_dma(s, a, r);
+    if (r.kernel == GemmKernel::Small8 || r.kernel == GemmKernel::Small3) return launch_gemm_nt_small(s, a, r);
     static PerDeviceOnce once;
     const hipError_t ea = once.run([&]() -> hipError_t {
-        constexpr int big = 2 * (KP * 128 + KP * 128) * 16;
+        constexpr int big = (int)gemm_reg_lds(128, 128);
         hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_kernel<4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         if (e != hipSuccess) return e;
         return hipFuncSetAttribute((const void*)gemm_nt_kernel<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
     });
     if (ea != hipSuccess) return ea;
-    const Tuning& tn = tuning();
-    // few tiles: one 128 x 128 tile keeps a CU busy for 1.8 us per 64 of K while the rest of the
-    // chip idles -- 64 x 64 tiles finish 4x sooner (panel-internal updates, diagonal blocks)
-    const int64_t tiles128 = (a.M / 128) * ((a.N + 127) / 128);
-    if (tn.gemm_small_tiles && tn.gemm_small_dma && !tn.gemm_dbg && tiles128 < 128 && gemm_small_eligible(a))
-        return launch_gemm_nt_small(s, a);
-    if (tn.gemm_small_tiles && !tn.gemm_dbg && tiles128 < 128) {
-        plan(a, 64, 64, p, nblocks);
-        constexpr size_t lds = 2 * (KP * 64 + KP * 64) * 16;
-        hipLaunchKernelGGL((gemm_nt_kernel<2, 2, false>), dim3(nblocks), dim3(256), lds, s, p);
-    } else if (a.N % 128 == 0) {
-        plan(a, 128, 128, p, nblocks);
-        constexpr size_t lds = 2 * (KP * 128 + KP * 128) * 16;
-        if (p.dbg) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true>), dim3(nblocks), dim3(256), lds, s, p);
-        else hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false>), dim3(nblocks), dim3(256), lds, s, p);
-    } else {
-        plan(a, 128, 64, p, nblocks);
-        constexpr size_t lds = 2 * (KP * 128 + KP * 64) * 16;
-        hipLaunchKernelGGL((gemm_nt_kernel<4, 2, false>), dim3(nblocks), dim3(256), lds, s, p);
+    GemmDev p;
+    int nblocks;
+    switch (r.kernel) {
+        case GemmKernel::Reg64:
+            plan(a, 64, 64, p, nblocks);
+            hipLaunchKernelGGL((gemm_nt_kernel<2, 2, false>), dim3(nblocks), dim3(256), r.lds, s, p);
+            break;
+        case GemmKernel::Reg128x64:
+            plan(a, 128, 64, p, nblocks);
+            hipLaunchKernelGGL((gemm_nt_kernel<4, 2, false>), dim3(nblocks), dim3(256), r.lds, s, p);
+            break;
+        case GemmKernel::Reg128:
+            plan(a, 128, 128, p, nblocks);
+            hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false>), dim3(nblocks), dim3(256), r.lds, s, p);
+            break;
+        case GemmKernel::Reg128Probe:
+            plan(a, 128, 128, p, nblocks);
+            hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true>), dim3(nblocks), dim3(256), r.lds, s, p);
+            break;
+        default:
+            return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -26,6 +26,8 @@ static thread_local const Tuning* t_tuning = nullptr;
 const Tuning& tuning() { return t_tuning ? *t_tuning : t_dev_tuning; }
 TuneScope::TuneScope(const Tuning* t) : prev(t_tuning) { t_tuning = t; }
 TuneScope::~TuneScope() { t_tuning = prev; }
+static thread_local Sharing t_sharing;
+Sharing& sharing() { return t_sharing; }
 }
 
 extern "C" {
@@ -805,7 +807,7 @@ int gpmi_lml_batch(gpmi_ctx* c, const double* triples, int64_t T, double* lml_ou
     auto work = [&](int r) {
         gpmi_ctx* l = lane[(size_t)r];
         TuneScope tune_scope(&l->tune);         // this lane's thread runs with this lane's options
-        GemmShallowScope shares_chip(false, L > 1);   // another lane's kernels run beside this one's: no launch takes the whole chip
+        SharingScope shares_chip(L > 1 ? sharing().and_chip_shared() : sharing());   // another lane's kernels run beside this one's: no launch takes the whole chip
         if (hipSetDevice(l->device) != hipSuccess) { lane_rc[(size_t)r] = GPMI_ERR_RUNTIME; lane_err[(size_t)r] = "hipSetDevice"; return; }
         for (int64_t t = r; t < T; t += L) {
             const double ell = triples[3 * t], sigma = triples[3 * t + 1], s2 = triples[3 * t + 2];

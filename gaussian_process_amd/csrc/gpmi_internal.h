@@ -6,6 +6,8 @@
 
 #include <mutex>
 
+#include "gpmi_route.h"
+
 namespace gpmi {
 
 constexpr int TILE = 128;   // row / column padding granule of every matrix
@@ -15,21 +17,11 @@ constexpr int IB = 64;      // inner (register-resident) panel width
 // context's set for the calling thread (TuneScope), so two contexts driven from two threads (the lanes
 // of gpmi_lml_batch) never see each other's settings.  The context-free gpmi_dev_* primitives run with
 // the defaults.
-struct Tuning {
-    int gemm_use_dma = 1;       // LDS-DMA GEMM for launches with >= 256 tiles
-    int gemm_small_tiles = 1;   // 64 x 64 tiles for launches with few tiles
-    int gemm_persist = 1;       // resident workgroups that chain the K loops of consecutive tiles (launches with >= 2 rounds of tiles)
-    int gemm_ticket = 0;        // ticket form of the per-tile kernel (resident workgroups, tiles drawn from counters, no state across tiles): 1 Cholesky trailing updates under lookahead, 2 every launch of at least one round
-    int gemm_balance = 1;       // per-tile launches: choose the supertile edge of mid-size triangular launches by the deal of blocks to the XCDs (gpmi_plan.h: plan_tri_xcd_efficiency); 0: always the widest
-    int gemm_dma_waves = 8;     // 4: one wave per SIMD, 8: two waves per SIMD (32 x 64 per wave)
-    int gemm_tall = 1;          // per-tile launches of the 8-wave kernel: 1 256 x 128 blocks (two tiles, 64 x 64 per wave) for launches of at least tall_min_tiles live tiles, 0 128 x 128 always
-    int tall_min_tiles = 12288; // see gemm_tall (below: N = 16384 one pass +1.3 % with the tall form, lookahead panels wait for twice-as-long workgroups)
+struct Tuning : GemmTuning {    // gpmi_route.h: the options that select a GEMM kernel
     int trsm_wave = 1;          // 1: wave-per-row substitution kernel for short panels, 0: lane-per-row always
     int rbf_blocks = 16384;     // persistent blocks of the register-path K build
     int trsv_vinv = 2;          // backward solve: 2 one launch, column blocks chained through the solution vector (inverted 128 x 128 diagonal blocks); 1 one launch per 128 unknowns with the same inverses; 0 the 16 x 16 rounds
     int panel_fused = 1;        // 1: fused multi-column panel kernels, 0: first-generation potf2 + substitution leaves
-    int gemm_small_dma = 1;     // 1: deep-prefetch LDS-DMA kernel for launches with few tiles, 0: first-generation 64 x 64 kernel
-    int gemm_dbg = 0;           // timing-only ablation bits (gpmi_probe_gemm); results are wrong when non-zero
     unsigned long long* gemm_stamps = nullptr;   // diagnostic stamp buffer (gpmi_probe_gemm variant bit 16)
     unsigned long long* panel_stamps = nullptr;  // diagnostic: s_memtime stamps of the panel kernels (gpmi_probe_panel)
 };
@@ -38,6 +30,14 @@ struct TuneScope {
     const Tuning* prev;
     explicit TuneScope(const Tuning* t);
     ~TuneScope();
+};
+// What else runs on the chip beside the launches of this thread (gpmi_route.h: Sharing): read by gemm_route and by
+// launch_trsm128; a driver that puts work on a second stream or lane says so for the length of a scope.
+Sharing& sharing();
+struct SharingScope {
+    const Sharing prev;
+    explicit SharingScope(Sharing s) : prev(sharing()) { sharing() = s; }
+    ~SharingScope() { sharing() = prev; }
 };
 
 // One-time, per-device opt-in (hipFuncSetAttribute for > 64 KiB of dynamic LDS): thread-safe, keyed by
@@ -86,26 +86,17 @@ struct GemmArgs {
     const int64_t* b_block_off = nullptr;
     int64_t b_block_rows = 0;
 };
-hipError_t launch_gemm_nt(hipStream_t s, const GemmArgs& a);
-bool gemm_nt_routes_dma(const GemmArgs& a);
-double gemm_nt_algorithmic_flops(const GemmArgs& a, int64_t real_rows);   // 2K per needed element (lower: on/below the diagonal)   // true when launch_gemm_nt hands this launch to the LDS-DMA kernel
-// gemm_dma.hip: one-workgroup-per-CU LDS-DMA variant (mode 0, N % 128 == 0)
-bool gemm_dma_eligible(const GemmArgs& a);
-hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a);
-// gemm_dma.hip: latency-oriented variant for launches with few tiles (64 x 64 tiles, eight K steps in flight)
-bool gemm_small_eligible(const GemmArgs& a);
-bool gemm_shallow_active();
-bool gemm_two_streams_active();
-// while alive on this thread: `on` -- small launches use the shallow ring and trsm128 its two-launch form (they run
-// beside a trailing update); `on` or `two_streams` -- the calling driver keeps two streams busy at once, so no launch
-// may take the whole chip for its whole length (the persistent GEMM form stays off)
-struct GemmShallowScope {
-    int prev, prev_two;
-    // exact: `on` == false switches the small-LDS forms OFF for the scope (default: an enclosing scope's setting stays)
-    explicit GemmShallowScope(bool on, bool two_streams = false, bool exact = false);
-    ~GemmShallowScope();
-};
-hipError_t launch_gemm_nt_small(hipStream_t s, const GemmArgs& a);
+// The route of a launch (gpmi_route.h: gemm_route; a launch that wants a resident form creates the device's counter
+// pool here), and the launch of a route -- for a caller that accounts by the kernel family it reaches.
+GemmRoute gemm_nt_route(const GemmArgs& a);
+hipError_t launch_gemm_nt(hipStream_t s, const GemmArgs& a, const GemmRoute& r);
+inline hipError_t launch_gemm_nt(hipStream_t s, const GemmArgs& a) { return launch_gemm_nt(s, a, gemm_nt_route(a)); }
+double gemm_nt_algorithmic_flops(const GemmArgs& a, int64_t real_rows);   // 2K per needed element (lower: on/below the diagonal)
+// gemm_dma.hip: the launches of the LDS-DMA kernels of a route (128 x 128 tiles and their forms; 64 x 64 tiles for
+// launches with few tiles), and the resident workgroups a launch of this device may use (0: no counter pool)
+hipError_t launch_gemm_nt_dma(hipStream_t s, const GemmArgs& a, const GemmRoute& r);
+hipError_t launch_gemm_nt_small(hipStream_t s, const GemmArgs& a, const GemmRoute& r);
+int gemm_resident_groups();
 // number of tiles the launch actually computes (for flop accounting)
 double gemm_nt_flops(const GemmArgs& a);
 

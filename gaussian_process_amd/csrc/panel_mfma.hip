@@ -590,7 +590,7 @@ hipError_t launch_trsm128(hipStream_t s, const double* L, int64_t ldl, double* X
     if (e != hipSuccess) return e;
     const int64_t nslabs = m / TRSM_ROWS;
     const unsigned grid = (unsigned)std::min<int64_t>(nslabs, 512);     // two workgroups per CU (72 KiB of LDS each)
-    if (gemm_shallow_active()) {            // beside a trailing update: two launches that fit next to its workgroups
+    if (sharing().small_lds) {            // beside a trailing update: two launches that fit next to its workgroups
         hipLaunchKernelGGL(trsm128_kernel<0>, dim3(grid), dim3(256), trsm_tiles<0>() * TILE_BYTES, s, L, ldl, X, ldx, nslabs,
                            tuning().panel_stamps);
         hipLaunchKernelGGL(trsm128_kernel<1>, dim3(grid), dim3(256), trsm_tiles<1>() * TILE_BYTES, s, L, ldl, X, ldx, nslabs,
