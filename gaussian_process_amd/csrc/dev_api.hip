@@ -242,11 +242,13 @@ int gpmi_dev_trsv_lt_chain(void* stream, double* L_dev, int64_t ld, double* vsid
 // Tell the block primitives called from this thread that they run beside a trailing update on another stream
 // (the multi-rank driver's lookahead): the panel kernels then use their small-LDS forms (two-launch trsm128, shallow
 // ring for small GEMMs), which fit on a CU next to an update workgroup and start at once.  Results are the
-// same bits either way.  0 switches back.
+// same bits either way.  2: the same, and no panel chain waits for the update launches of this thread either
+// (Sharing::panel_slack: the 256 x 128 form from tall_min_tiles_slack live tiles on).  0 switches back.
 int gpmi_dev_set_concurrent(int on) {
     static thread_local bool active = false;
     static thread_local Sharing before;
-    if (on && !active) { before = sharing(); sharing() = Sharing::beside_update(); }
+    if (on && !active) before = sharing();
+    if (on) sharing() = Sharing::beside_update().with_panel_slack(on == 2);
     if (!on && active) sharing() = before;
     active = on != 0;
     return GPMI_OK;

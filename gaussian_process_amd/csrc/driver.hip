@@ -104,11 +104,14 @@ std::vector<int64_t> block_schedule(const gpmi_ctx* c, int64_t ncols) {
 // A; rows ncols..nrows-1 are carried along (they end up multiplied by L^-T).
 //
 // With lookahead the trailing update of step k is split in two launches: (a) the next
-// block column only and (b) the rest.  From 49152 columns up both run on the main stream, the panel
-// stream (high priority) factors panel k+1 behind (a), concurrently with (b).  Below that (a) itself goes
-// on the panel stream, right behind panel k and in front of panel k+1, (b) on the main stream.  (a) and (b) write different columns
+// block column only and (b) the rest.  (a) goes on the panel stream (high priority), right behind panel k and in
+// front of panel k+1, (b) on the main stream.  (a) and (b) write different columns
 // and both only read panel k, so they start together: the tail of (a) -- a launch whose last
 // tiles leave most CUs idle -- and the whole latency-bound panel k+1 run under (b).
+// (Option "slack_forms" without bit 1: from 49152 columns up (a) then (b) on the main stream, panel k+1 behind (a).)
+// From 49152 columns up the panel chain is 4-5x shorter than the step it runs under, so nothing on the critical path
+// waits for a workgroup that holds its CU twice as long: the launches of such a factorisation -- (a), (b) and the
+// updates inside the panel -- take the 256 x 128 form from tall_min_tiles_slack live tiles on (Sharing::panel_slack).
 // Dependencies:
 //   panel k  ->  (a)_k                 (same stream)
 //   panel k  ->  (b)_k                 (main waits on the panel event)
@@ -127,11 +130,15 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
     // panel kernels beside the trailing update use their small-LDS forms -- while there IS a trailing update of some length
     // to run beside: once the columns right of the panel are fewer than c->shallow_min, part (b) of a step is over long
     // before the panel chain is, and the one-launch forms (which then find empty CUs) are the shorter chain
-    SharingScope shallow((la || follow) ? Sharing::beside_update() : sharing());
+    const bool large = la && ncols >= 49152;
+    const bool slack = large && (c->slack_forms & 1);
+    SharingScope shallow((la || follow) ? Sharing::beside_update().with_panel_slack(slack) : sharing());
     // (a) on the panel stream pays at mid sizes (N = 16384: -4 %, 32768: -1 %), where a launch's tail and the
-    // panel chain are a visible share of a step; at the headline size it is worth 0.4 % and would put two
-    // trailing-update launches in flight at once, which makes "time per launch" (the roofline figure) ambiguous
-    const bool col_on_panel = la && ncols < 49152;
+    // panel chain are a visible share of a step.  At the headline size the tail of (a) is a smaller share, but a
+    // 256 x 128 tail is twice as long as the 128 x 128 one: (a) runs beside (b) there as well (the numbers:
+    // LAB_NOTES.md, "leftover 128 x 128 updates").  (a) is then timed with the panel and launched under the generic
+    // symbol at every size: "time per launch" (the roofline figure) covers the (b) launches only
+    const bool col_on_panel = la && (!large || (c->slack_forms & 2));
     const int slot_p = account ? GPMI_T_CHOL_PANEL : GPMI_T_COUNT - 1;
     const int slot_t = account ? GPMI_T_CHOL_TRAIL : GPMI_T_COUNT - 1;
     if (la && (e = c->order(sm, sp_)) != hipSuccess) return e;   // panel 0 after the K build
@@ -170,7 +177,7 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         size_t sp = c->span_begin(slot_p, sp_);
         {
             SharingScope panel_forms(!la ? sharing().large_lds()
-                                     : ncols - k >= c->shallow_min ? Sharing::beside_update() : Sharing::chip_shared_only());
+                                     : (ncols - k >= c->shallow_min ? Sharing::beside_update() : Sharing::chip_shared_only()).with_panel_slack(slack));
             e = panel_factor(sp_, A + k * ld + k, ld, nb, nrows - k, k, info);
         }
         c->span_end(sp, sp_);
@@ -192,6 +199,7 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
                 g.ldc = g.lda = follow->ldv; g.ldb = ld;
                 g.M = follow->m; g.N = ncols - r0; g.K = nb;
                 g.mode = 0; g.lower = 0; g.diag_off = 0;
+                SharingScope update_forms(sharing().with_panel_slack(false));       // the following rows keep their forms
                 if ((e = launch_gemm_nt(follow->vs, g)) != hipSuccess) return e;
             }
         }
@@ -203,7 +211,7 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         }
         const int64_t nbn = widths[step + 1];
         if (!col_on_panel) {
-            // large problems: (a) then (b) on the main stream, panel k+1 behind (a)
+            // (a) then (b) on the main stream, panel k+1 behind (a)
             if ((e = trail(sm, true, r0, r0, r0 - nb, nb, nbn)) != hipSuccess) return e;
             if ((e = c->order(sm, sp_)) != hipSuccess) return e;
             if (r0 + nbn < ncols &&

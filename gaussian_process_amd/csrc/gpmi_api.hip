@@ -63,6 +63,7 @@ int gpmi_ctx_create(int device, gpmi_ctx** out) {
     if ((env = getenv("GPMI_NB"))) c->nb = std::max<int64_t>(128, atoll(env) / 128 * 128);
     if ((env = getenv("GPMI_LD_PAD"))) c->ld_pad = std::max<int64_t>(0, atoll(env) / 2 * 2);
     if ((env = getenv("GPMI_LOOKAHEAD"))) c->lookahead = atoi(env) ? 1 : 0;
+    if ((env = getenv("GPMI_SLACK_FORMS"))) c->slack_forms = atoi(env) & 3;
     *out = c;
     return GPMI_OK;
 }
@@ -117,6 +118,9 @@ static int set_tuning_option(Tuning& t, const char* name, int64_t value) {
     } else if (!strcmp(name, "tall_min_tiles")) {
         if (value < 0 || value > (1 << 30)) return fail_arg("tall_min_tiles must be in 0..2^30");
         t.tall_min_tiles = (int)value;
+    } else if (!strcmp(name, "tall_min_tiles_slack")) {
+        if (value < 0 || value > (1 << 30)) return fail_arg("tall_min_tiles_slack must be in 0..2^30");
+        t.tall_min_tiles_slack = (int)value;
     } else if (!strcmp(name, "gemm_dma")) {
         t.gemm_use_dma = value ? 1 : 0;
     } else {
@@ -144,6 +148,9 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "shallow_min")) {
         if (value < 0) return fail_arg("shallow_min must be >= 0");
         c->shallow_min = value;
+    } else if (!strcmp(name, "slack_forms")) {
+        if (value < 0 || value > 3) return fail_arg("slack_forms: bit 0 the lower bar of the 256 x 128 form, bit 1 the next block column on the panel stream");
+        c->slack_forms = (int)value;
     } else if (!strcmp(name, "one_pass_form")) {
         if (value < 0 || value > 2) return fail_arg("one_pass_form must be 0 (by size), 1 (rows ride) or 2 (rows follow)");
         c->one_pass_form = (int)value;

@@ -104,6 +104,8 @@ struct gpmi_ctx {
                             // profiles/r04_la_min_sweep.txt -- one pass / two calls / fit alone at N = 4096: 3.06 -> 2.96 / 3.82 -> 3.86 /
                             // 2.56 -> 2.59 ms, 6144: 5.41 -> 5.20 / 6.69 -> 6.50 / 4.67 -> 4.48, 10240: 13.8 -> 12.6 / 15.9 -> 14.7; same bits)
     int64_t shallow_min = 6144; // under lookahead, panels with fewer columns left than this use the one-launch panel kernels (0: never)
+    int slack_forms = 3;    // Cholesky of 49152 columns and more (the panel chain has slack), bit mask: 1 the 256 x 128 update form from
+                            // tall_min_tiles_slack live tiles on (Sharing::panel_slack), 2 part (a) of a step on the panel stream as below 49152
     int one_pass_form = 0;  // gpmi_fit_predict_resident: 1 the test set's rows ride in the panel and update launches, 2 they follow on a
                             // stream of their own (panel k done -> their solve against L_kk -> their update), 0 = by size
     int lanes = 0;          // gpmi_lml_batch: factorisations in flight (0 = by size)

@@ -20,7 +20,8 @@ struct GemmTuning {
     int gemm_balance = 1;       // per-tile launches: choose the supertile edge of mid-size triangular launches by the deal of blocks to the XCDs (gpmi_plan.h: plan_xcd_efficiency); 0: always the widest
     int gemm_dma_waves = 8;     // 4: one wave per SIMD, 8: two waves per SIMD (32 x 64 per wave)
     int gemm_tall = 1;          // per-tile launches of the 8-wave kernel: 1 256 x 128 blocks (two tiles, 64 x 64 per wave) for launches of at least tall_min_tiles live tiles, 0 128 x 128 always
-    int tall_min_tiles = 12288; // see gemm_tall (below: N = 16384 one pass +1.3 % with the tall form, lookahead panels wait for twice-as-long workgroups)
+    int tall_min_tiles = 12288; // see gemm_tall (below: N = 16384 one pass +1.3 % with the tall form, lookahead panels wait for twice-as-long workgroups) -- the bar of every launch outside Sharing::panel_slack
+    int tall_min_tiles_slack = 1024;    // the same bar for launches under Sharing::panel_slack (a Cholesky of 49152 columns and more: its panel chain has 4-5x slack, nothing waits for the longer workgroups)
     int gemm_small_dma = 1;     // 1: deep-prefetch LDS-DMA kernel for launches with few tiles, 0: first-generation 64 x 64 kernel
     // timing-only ablation bits (gpmi_probe_gemm); results are wrong when non-zero.  Non-zero keeps small launches off
     // the 64 x 64 kernels; 1 .. 255 keeps a launch off the LDS-DMA kernels, >= 256 does not; the low byte selects the
@@ -37,12 +38,18 @@ struct Sharing {
     // another stream or lane keeps part of the chip busy: no launch may take the whole chip for its whole length (the
     // persistent form stays off), and gemm_ticket == 1 applies to the trailing updates
     bool chip_shared = false;
+    // the launch belongs to a factorisation whose lookahead panel chain is far off the critical path (cholesky_inplace
+    // from 49152 columns up: ~9 ms of panel kernels per ~50 ms step): the 256 x 128 form from tall_min_tiles_slack
+    // live tiles on instead of tall_min_tiles -- the next-block-column launches, the late trailing updates and the
+    // updates inside the panel
+    bool panel_slack = false;
 
     static Sharing alone() { return Sharing(); }
     static Sharing chip_shared_only() { Sharing s; s.chip_shared = true; return s; }
     static Sharing beside_update() { Sharing s; s.small_lds = s.chip_shared = true; return s; }
-    Sharing and_chip_shared() const { Sharing s = *this; s.chip_shared = true; return s; }     // small_lds as it is
-    Sharing large_lds() const { Sharing s = *this; s.small_lds = false; return s; }            // chip_shared as it is
+    Sharing and_chip_shared() const { Sharing s = *this; s.chip_shared = true; return s; }     // the others as they are
+    Sharing large_lds() const { Sharing s = *this; s.small_lds = false; return s; }            // the others as they are
+    Sharing with_panel_slack(bool on) const { Sharing s = *this; s.panel_slack = on; return s; }
 };
 
 // Every kernel symbol a launch can reach.  Trail: the same code under the Cholesky trailing update's own symbol
@@ -172,10 +179,12 @@ inline void gemm_route(const GemmRouteIn& in, GemmRoute& r) {
     }
     // one workgroup per block (no pool, or too few blocks for a resident form: the same bits): the supertile edge is
     // chosen with the static deal of blocks to the XCDs in mind.  256 x 128 blocks, as a pair plan with the same
-    // supertiles, for launches of the 8-wave kernel with enough live tiles
+    // supertiles, for launches of the 8-wave kernel with enough live tiles (the bar: tall_min_tiles, or the lower
+    // tall_min_tiles_slack where no panel chain waits for the longer workgroups)
     const bool balance = tn.gemm_balance != 0;
+    const int tall_bar = in.sharing.panel_slack ? tn.tall_min_tiles_slack : tn.tall_min_tiles;
     const bool tall = eight && tn.gemm_tall &&
-                      plan_live_tiles(Tm, Tn, in.lower, in.diag_off, in.row_ncols_host, in.row_bands, in.row_block_tiles) >= tn.tall_min_tiles;
+                      plan_live_tiles(Tm, Tn, in.lower, in.diag_off, in.row_ncols_host, in.row_bands, in.row_block_tiles) >= tall_bar;
     if ((balance || tall) && !plan(balance, tall)) return done(GemmKernel::Invalid, 0, 0);
     const GemmKernel trail_or = !eight ? GemmKernel::Dma4 : in.role == 1 ? (tall ? GemmKernel::TallTrail : GemmKernel::Dma8Trail)
                                                                          : (tall ? GemmKernel::Tall : GemmKernel::Dma8);

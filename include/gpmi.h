@@ -75,11 +75,17 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
  *               count as "last" (0: three), when "nb" is automatic.  Until round 2 any non-zero value meant "up and
  *               down": that is 3 now; other bits or a negative value are refused),
  *               "shallow_min" (under lookahead, panels with fewer columns left than this use the one-launch panel
- *               kernels: the update they would run beside is over long before they are; default 6144, 0 = never);
+ *               kernels: the update they would run beside is over long before they are; default 6144, 0 = never),
+ *               "slack_forms" (a Cholesky of 49152 columns and more, whose lookahead panel chain is far off the critical
+ *               path; bit mask, default 3: 1 its update launches take the 256 x 128 form from "tall_min_tiles_slack" live
+ *               tiles on instead of "tall_min_tiles", 2 the update of the next block column runs on the panel stream
+ *               beside the rest of the step, as it does below 49152 columns; same results whatever the value);
  *               kernel selection (for measurements; also per context -- the lanes of gpmi_lml_batch inherit them):
  *               "panel_fused" (0/1: 128-column MFMA panel kernels / first-generation 64-column leaves),
  *               "gemm_dma" (0/1), "gemm_dma_waves" (4/8), "gemm_small_tiles" (0/1), "gemm_small_dma" (0/1),
  *               "gemm_persist" (0/1: resident workgroups for update GEMMs that have the chip to themselves),
+ *               "gemm_tall" (0/1: 256 x 128 blocks for per-tile update launches of at least "tall_min_tiles" live
+ *               128 x 128 tiles, default 12288 -- "tall_min_tiles_slack", default 1024, under "slack_forms" bit 0),
  *               "trsv_vinv" (backward solve: 2 ONE launch, column blocks chained through the solution vector, with the
  *               inverted 128 x 128 diagonal blocks -- the default; 1 one launch per block with the same inverses; 0 the
  *               16 x 16 rounds),
@@ -359,7 +365,9 @@ int gpmi_dev_trsv_lt_vinv(void* stream, double* L_dev, int64_t ld, double* b_dev
 int gpmi_dev_trsv_lt_chain(void* stream, double* L_dev, int64_t ld, double* vside_dev, const double* m_dev, double* x_dev,
                            int64_t n, int invert, int* err_dev);
 /* on != 0: the block primitives called from this thread run beside a trailing update on another stream (lookahead)
- * and use their small-LDS forms, which fit on a CU next to an update workgroup; same results.  0 switches back. */
+ * and use their small-LDS forms, which fit on a CU next to an update workgroup; same results.  2: the same, and no
+ * panel chain waits for this thread's update launches either (the state of a Cholesky of 49152 columns and more: the
+ * 256 x 128 form from "tall_min_tiles_slack" live tiles on); same results.  0 switches back. */
 int gpmi_dev_set_concurrent(int on);
 /* kernel-selection options (the gpmi_set_option names that choose between kernel forms: "gemm_ticket", "gemm_persist",
  * "gemm_tall", ...) for the context-free block primitives called from THIS thread; same results
