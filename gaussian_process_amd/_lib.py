@@ -20,7 +20,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgpmi355x.so")
 
 GPMI_OK, GPMI_ERR_NOT_PD, GPMI_ERR_BAD_ARG, GPMI_ERR_RUNTIME = 0, 1, 2, 3
-ABI_VERSION = 3
+ABI_VERSION = 4
+SOFTMAX_MAX_CLASSES = 10     # GPMI_SOFTMAX_MAX_CLASSES of include/gpmi.h
 
 # stage-timer slots (enum in gpmi.h)
 T_KBUILD, T_CHOL, T_CHOL_PANEL, T_CHOL_TRAIL, T_LML, T_KS, T_SOLVE_V, T_MEANVAR, \
@@ -65,6 +66,9 @@ SIGNATURES = {
     "gpmi_lml_batch": [_vp, _dp, _i64, _dp, C.POINTER(C.c_int)],
     "gpmi_laplace_fit": [_vp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp],
     "gpmi_laplace_predict_resident": [_vp, _dp, _dp, _dp],
+    "gpmi_softmax_fit": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int),
+                         C.POINTER(C.c_int), _dp],
+    "gpmi_softmax_predict_resident": [_vp, _dp, _dp, _i64, _dp, _dp],
     "gpmi_get_timers": [_vp, _dp, C.c_int],
     "gpmi_sync": [_vp],
     "gpmi_probe_mfma_f64": [_vp, _dp],

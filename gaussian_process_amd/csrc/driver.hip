@@ -300,7 +300,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (rc) return rc;
     hipStream_t s = c->stream;
     c->have_factor = false;
-    c->have_laplace = false;          // a regression factorisation replaces a resident Laplace fit
+    c->have_laplace = c->have_softmax = false;          // a regression factorisation replaces a resident Laplace or softmax fit
     c->v_in_A = false;
     c->have_vinv = false;
     c->have_vside = false;

@@ -76,7 +76,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->lap, &c->lap_part, &c->lap_out})
+                       &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -137,7 +137,7 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "ld_pad")) {
         if (value < 0 || value % 2) return fail_arg("ld_pad must be even and >= 0");
         c->ld_pad = value;
-        c->have_factor = c->have_v = c->have_laplace = false;
+        c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
     } else if (!strcmp(name, "timing")) {
         c->timing = value ? 1 : 0;
     } else if (!strcmp(name, "lookahead")) {
@@ -184,7 +184,7 @@ int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
     if (kind < 0 || kind > 2) return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear) or 2 (periodic)");
     if (kind == 2 && (!(p0 != 0.0) || !(p1 != 0.0))) return fail_arg("gpmi_set_kernel: period and lengthscale must be non-zero");
     c->kind = kind; c->kp0 = p0; c->kp1 = p1;
-    c->have_factor = c->have_v = c->have_laplace = false;
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
     return GPMI_OK;
 }
 
@@ -200,7 +200,7 @@ int gpmi_set_kernel_params(gpmi_ctx* c, int kind, const double* params, int npar
         return fail_arg("gpmi_set_kernel_params: theta_2, 4, 5, 7, 8, 10 divide and must be non-zero");
     c->kind = 3;
     for (int i = 0; i < 11; ++i) c->kpv[i] = params[i];
-    c->have_factor = c->have_v = c->have_laplace = false;
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
     return GPMI_OK;
 }
 
@@ -299,7 +299,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (!c || !X || !y) return fail_arg("gpmi_set_train: null argument");
     if (N <= 0 || d <= 0) return fail_arg("gpmi_set_train: N and d must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = false;
+    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = c->have_softmax = false;
     HIP_TRY(c->X.ensure((size_t)N * d * 8));
     HIP_TRY(c->y.ensure((size_t)N * 8));
     HIP_TRY(hipMemcpyAsync(c->X.p, X, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream));
@@ -863,6 +863,22 @@ int gpmi_laplace_predict_resident(gpmi_ctx* c, double* f_mean, double* f_var, do
     if (!c) return fail_arg("gpmi_laplace_predict: null context");
     HIP_TRY(hipSetDevice(c->device));
     return laplace_predict_impl(c, f_mean, f_var, prob);
+}
+
+// Multi-class GP classification, GPML Algorithms 3.3 / 3.4 with the softmax likelihood (softmax.hip)
+int gpmi_softmax_fit(gpmi_ctx* c, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
+                     int* iters, int* converged, double* f_hat) {
+    if (!c) return fail_arg("gpmi_softmax_fit: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    TuneScope tune_scope(&c->tune);
+    return softmax_fit_impl(c, n_classes, sigma, ell, tol, max_iter, log_q, iters, converged, f_hat);
+}
+
+int gpmi_softmax_predict_resident(gpmi_ctx* c, double* mu, double* cov, int64_t n_samples, const double* normals,
+                                  double* prob) {
+    if (!c) return fail_arg("gpmi_softmax_predict: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return softmax_predict_impl(c, mu, cov, n_samples, normals, prob);
 }
 
 int gpmi_get_timers(gpmi_ctx* c, double* stage_ms, int count) {

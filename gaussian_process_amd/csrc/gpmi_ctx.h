@@ -158,6 +158,13 @@ struct gpmi_ctx {
     // (and anything else that clears have_factor) clears have_laplace.
     bool have_laplace = false;
     DevBuf lap, lap_part, lap_out;
+    // multi-class classification (softmax.hip): A holds M = chol(sum_c E_c) at the mode, sm_E the C matrices -E_c (full,
+    // symmetric), sm the C x Np vectors (Y - P among them).  The rule above extended by one flag: a softmax fit clears
+    // have_factor and have_laplace, a regression or binary fit clears have_softmax.  K and V = S_c L_c^-T are scratch of
+    // the fit and live in Kn and U (the scratch of gpmi_lml_grad).
+    bool have_softmax = false;
+    int sm_classes = 0;
+    DevBuf sm, sm_part, sm_E, sm_B, sm_out;
     // timers
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -245,5 +252,11 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
                      int* converged, double* f_hat);
 int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob);
 void laplace_quad_nodes(double sig2, int* M, double* T, double* h);
+
+// softmax.hip: GPML Algorithms 3.3 (Newton iteration for the mode, softmax likelihood, C latent functions with one shared
+// prior) and 3.4 (prediction)
+int softmax_fit_impl(gpmi_ctx* c, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
+                     int* iters, int* converged, double* f_hat);
+int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t n_samples, const double* normals, double* prob);
 
 }  // namespace gpmi

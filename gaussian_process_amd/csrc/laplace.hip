@@ -14,25 +14,13 @@
 //   laplace_quad_kernel         prediction: V* = sigma^2 - |v|^2 and pi* = int expit(z) N(z | f*, V*) dz
 // Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
 #include "gpmi_ctx.h"
+#include "lap_dev.h"
 
 namespace gpmi {
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-constexpr int LT = 128;        // tile edge (TILE)
-constexpr int SYMV_THREADS = 256;
-constexpr int VEC_THREADS = 256;
-
-// lower tile t (row-major enumeration of the lower triangle) -> (I, J), J <= I
-__device__ __forceinline__ void tile_of(int64_t t, int64_t& I, int64_t& J) {
-    int64_t i = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (i * (i + 1) / 2 > t) --i;
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    I = i;
-    J = t - i * (i + 1) / 2;
-}
+using namespace lapdev;      // d2, LT, SYMV_THREADS, VEC_THREADS, tile_of, slot_sum, wg_reduce2
 
 __device__ __forceinline__ double expit(double z) {
     if (z >= 0.0) return 1.0 / (1.0 + exp(-z));
@@ -149,31 +137,6 @@ __global__ __launch_bounds__(SYMV_THREADS) void laplace_symv_kernel(double* __re
             part[(I * nt + J) * LT + t] = rowsum[t];
             part[(J * nt + I) * LT + t] = cs;
         }
-    }
-}
-
-// y_i = sum_b slot (i / 128, b)[i % 128], b in index order
-__device__ __forceinline__ double slot_sum(const double* __restrict__ part, int64_t nt, int64_t i) {
-    const double* p = part + (i / LT) * nt * LT + (i % LT);
-    double acc = 0.0;
-    for (int64_t b = 0; b < nt; ++b) acc += p[b * LT];
-    return acc;
-}
-
-// fixed-order reduction of two values over the workgroup; valid in thread 0
-__device__ __forceinline__ void wg_reduce2(double& a, double& b, double* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        b += __shfl_down(b, off, 64);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { sh[2 * wave] = a; sh[2 * wave + 1] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double sa = 0., sb = 0.;
-        for (int v = 0; v < (int)(blockDim.x >> 6); ++v) { sa += sh[2 * v]; sb += sh[2 * v + 1]; }
-        a = sa; b = sb;
     }
 }
 
@@ -365,6 +328,7 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     // the Laplace factor replaces whatever was resident: no regression state survives
     c->have_factor = false;
     c->have_laplace = false;
+    c->have_softmax = false;
     c->v_in_A = false;
     c->have_vinv = false;
     c->have_vside = false;

@@ -1,0 +1,747 @@
+// Multi-class GP classification by the Laplace approximation (Rasmussen & Williams, GPML, Algorithms 3.3 and 3.4, softmax
+// likelihood, labels 0 .. C-1, one latent function per class, all with the same squared-exponential prior): the
+// memory-bound kernels around the existing hot path and the Newton driver.
+//
+// Per Newton step the O(N^3) work is C x [Cholesky of B_c = I + s_c s_c^T o K, the triangular sweep V_c = S_c L_c^-T,
+// the lower NT GEMM V_c V_c^T = E_c] and the Cholesky of sum_c E_c, all by the drivers of driver.hip.  K is built once
+// per fit and kept (the C factorisations of a step all start from it).  What is new here:
+//   softmax_symv_kernel<NV>  one matrix times up to C vectors over its lower tiles: F = A K and K B in ONE read of K's
+//                            lower triangle from memory (NV vectors per pass over a tile, the tile's later passes come
+//                            from cache), and E_c x_c for all classes in one launch (one matrix per blockIdx.y)
+//   softmax_bmat_kernel      A <- I + s_c s_c^T o K on the lower tiles, from the kept K
+//   softmax_newton_kernel    per point: F from the tile partials (or the halved step), P, sqrt(P), Y - P,
+//                            B = P o F - P o sum_c(P o F) + Y - P and the partials of Psi (max-subtracted logsumexp)
+//   softmax_psi_kernel       Psi in a fixed order with the Cholesky's pivot word and the backward solve's give-up word
+//   softmax_vec_kernel       C vectors from the tile partials (K b_c; c_c = E_c K b_c and sum_c c_c)
+//   softmax_esum_kernel      A <- sum_c E_c on the lower tiles (identity on the padding)
+//   softmax_update_kernel    A <- B - C + [E_c t]_c (keeping the previous A, F for step halving)
+//   softmax_mirror_kernel    lower triangle of every E_c -> its upper triangle (prediction multiplies by the full matrix)
+//   softmax_rowdot_kernel    prediction: mu* = R (Y - P)^T and B_c[i] . R[i]
+//   softmax_gram_kernel      prediction: Sigma[i] = [U_c[:, i] . U_c'[:, i]] + diag(sigma^2 - B_c[i] . R[i])
+//   softmax_sample_kernel    prediction: C x C Cholesky per test point and the mean of softmax(mu* + chol(Sigma) z_s)
+// The GEMM that forms V V^T subtracts (the fast route of gemm_nt): the buffers hold -E_c, and every consumer here takes
+// the sign back.  Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
+#include "gpmi_ctx.h"
+#include "lap_dev.h"
+
+namespace gpmi {
+
+namespace {
+
+using namespace lapdev;
+
+constexpr int MAXC = GPMI_SOFTMAX_MAX_CLASSES;
+constexpr int MT = 32;         // sub-tile edge of the mirror kernel
+
+struct SymvArgs {
+    const double* M;           // matrix m at M + m * mstride, leading dimension ld, nt x nt tiles (lower ones are read)
+    int64_t mstride, ld, nt;
+    const double* x;           // vector v of matrix m at x + m * xstride + v * nt * 128
+    int64_t xstride;
+    int nvec;                  // vectors per matrix
+    double* part;              // tile partials of (m, v) at part + (m * nvec + v) * nt * nt * 128
+};
+
+// The multi-vector form of laplace_symv_kernel<false>: one workgroup per lower tile (I, J), the same lane layout
+// (lane (g, q) of wave w reads row 32 * step + 8 * w + g at columns 16 k + 2 q (+1): every 16-byte load of a wave covers
+// one whole 128-byte line of eight rows), the same slots: slot (I, J) <- K_IJ x_J, slot (J, I) <- K_IJ^T x_I, the diagonal
+// tile puts both halves of its lower triangle into slot (I, I).  The vectors' tile segments sit in LDS; the column
+// accumulators (16 per vector and lane) bound NV.
+template <int NV>
+__global__ __launch_bounds__(SYMV_THREADS) void softmax_symv_kernel(SymvArgs p) {
+    __shared__ __attribute__((aligned(16))) double xs[2][NV][LT];      // [0]: x_J, [1]: x_I
+    __shared__ double rowsum[NV][LT];
+    __shared__ double colsum[SYMV_THREADS / 64][NV][LT];
+    int64_t I, J;
+    tile_of(blockIdx.x, I, J);
+    const bool diag = I == J;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 3, q = lane & 7;
+    const int64_t m = blockIdx.y, Np = p.nt * LT, pstride = p.nt * p.nt * LT;
+    const double* T = p.M + m * p.mstride + I * LT * p.ld + J * LT;
+    const double* xm = p.x + m * p.xstride;
+    double* pm = p.part + m * p.nvec * pstride;
+    for (int v0 = 0; v0 < p.nvec; v0 += NV) {
+        for (int e = threadIdx.x; e < 2 * NV * LT; e += SYMV_THREADS) {
+            const int which = e / (NV * LT), j = (e / LT) % NV, t = e % LT;
+            xs[which][j][t] = v0 + j < p.nvec ? xm[(int64_t)(v0 + j) * Np + (which ? I : J) * LT + t] : 0.0;
+        }
+        __syncthreads();
+        double cacc[NV][16];
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) cacc[j][k] = 0.0;
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            const int r = 32 * st + 8 * w + g;
+            d2 kv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) kv[k] = *reinterpret_cast<const d2*>(T + (int64_t)r * p.ld + 16 * k + 2 * q);
+            if (diag) {                                   // lower triangle only
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int c0 = 16 * k + 2 * q;
+                    if (c0 > r) kv[k].x = 0.0;
+                    if (c0 + 1 > r) kv[k].y = 0.0;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const double xr = xs[1][j][r];
+                double rp = 0.0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int c0 = 16 * k + 2 * q;
+                    const d2 xv = *reinterpret_cast<const d2*>(&xs[0][j][c0]);
+                    rp = fma(kv[k].x, xv.x, rp);
+                    rp = fma(kv[k].y, xv.y, rp);
+                    // column part: the diagonal tile's diagonal belongs to the row part
+                    cacc[j][2 * k] = fma((diag && c0 == r) ? 0.0 : kv[k].x, xr, cacc[j][2 * k]);
+                    cacc[j][2 * k + 1] = fma((diag && c0 + 1 == r) ? 0.0 : kv[k].y, xr, cacc[j][2 * k + 1]);
+                }
+                rp += __shfl_xor(rp, 1, 64);
+                rp += __shfl_xor(rp, 2, 64);
+                rp += __shfl_xor(rp, 4, 64);
+                if (q == 0) rowsum[j][r] = rp;
+            }
+        }
+        // column part: sum over the eight row groups of the wave, then over the four waves (fixed order)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                double v = cacc[j][k];
+                v += __shfl_xor(v, 8, 64);
+                v += __shfl_xor(v, 16, 64);
+                v += __shfl_xor(v, 32, 64);
+                cacc[j][k] = v;
+            }
+            if (g == 0) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    colsum[w][j][16 * k + 2 * q] = cacc[j][2 * k];
+                    colsum[w][j][16 * k + 2 * q + 1] = cacc[j][2 * k + 1];
+                }
+            }
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < NV * LT; e += SYMV_THREADS) {
+            const int j = e / LT, t = e % LT;
+            if (v0 + j >= p.nvec) continue;
+            double* pv = pm + (int64_t)(v0 + j) * pstride;
+            const double cs = ((colsum[0][j][t] + colsum[1][j][t]) + colsum[2][j][t]) + colsum[3][j][t];
+            if (diag) {
+                pv[(I * p.nt + I) * LT + t] = rowsum[j][t] + cs;
+            } else {
+                pv[(I * p.nt + J) * LT + t] = rowsum[j][t];
+                pv[(J * p.nt + I) * LT + t] = cs;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// One workgroup per lower tile: out = I + s s^T o K (real rows and columns only, the padding becomes exactly the
+// identity).  Diagonal tiles are written whole, from K's lower triangle.
+__global__ __launch_bounds__(VEC_THREADS) void softmax_bmat_kernel(const double* __restrict__ K, double* __restrict__ out,
+                                                                   int64_t ld, int64_t N, const double* __restrict__ s) {
+    int64_t I, J;
+    tile_of(blockIdx.x, I, J);
+    const bool diag = I == J;
+    for (int e = threadIdx.x; e < LT * LT / 2; e += VEC_THREADS) {
+        const int r = e / (LT / 2), c0 = 2 * (e % (LT / 2));
+        const int64_t gi = I * LT + r, gj = J * LT + c0;
+        double k0, k1;
+        if (!diag) {
+            const d2 kv = *reinterpret_cast<const d2*>(K + gi * ld + gj);
+            k0 = kv.x; k1 = kv.y;
+        } else {
+            k0 = c0 <= r ? K[gi * ld + gj] : K[gj * ld + gi];
+            k1 = c0 + 1 <= r ? K[gi * ld + gj + 1] : K[(gj + 1) * ld + gi];
+        }
+        const double si = s[gi];
+        double b0 = (gi < N && gj < N) ? (si * s[gj]) * k0 : 0.0;
+        double b1 = (gi < N && gj + 1 < N) ? (si * s[gj + 1]) * k1 : 0.0;
+        if (gi == gj) b0 = 1.0 + b0;
+        if (gi == gj + 1) b1 = 1.0 + b1;
+        *reinterpret_cast<d2*>(out + gi * ld + gj) = d2{b0, b1};
+    }
+}
+
+// One workgroup per lower tile: out = sum_c E_c = -(sum_c nE_c), classes in index order; 1 on the padded diagonal.
+// Diagonal tiles are written whole, from the lower triangles.
+__global__ __launch_bounds__(VEC_THREADS) void softmax_esum_kernel(const double* __restrict__ nE, int64_t estride, int C,
+                                                                   double* __restrict__ out, int64_t ld, int64_t N) {
+    int64_t I, J;
+    tile_of(blockIdx.x, I, J);
+    const bool diag = I == J;
+    for (int e = threadIdx.x; e < LT * LT / 2; e += VEC_THREADS) {
+        const int r = e / (LT / 2), c0 = 2 * (e % (LT / 2));
+        const int64_t gi = I * LT + r, gj = J * LT + c0;
+        const int64_t o0 = (!diag || c0 <= r) ? gi * ld + gj : gj * ld + gi;
+        const int64_t o1 = (!diag || c0 + 1 <= r) ? gi * ld + gj + 1 : (gj + 1) * ld + gi;
+        double a0 = 0.0, a1 = 0.0;
+        for (int c = 0; c < C; ++c) {
+            a0 += nE[c * estride + o0];
+            a1 += nE[c * estride + o1];
+        }
+        a0 = -a0; a1 = -a1;
+        if (gi == gj && gi >= N) a0 = 1.0;
+        if (gi == gj + 1 && gi >= N) a1 = 1.0;
+        *reinterpret_cast<d2*>(out + gi * ld + gj) = d2{a0, a1};
+    }
+}
+
+// blockIdx.x: lower 32 x 32 sub-tile (bi, bj) of matrix blockIdx.y; (bj, bi) <- its transpose (the diagonal sub-tile's
+// upper triangle from its lower one)
+__global__ __launch_bounds__(VEC_THREADS) void softmax_mirror_kernel(double* __restrict__ E, int64_t estride, int64_t ld) {
+    __shared__ double t[MT][MT + 1];
+    int64_t bi, bj;
+    tile_of(blockIdx.x, bi, bj);
+    double* M = E + (int64_t)blockIdx.y * estride;
+    const int tx = threadIdx.x % MT, ty = threadIdx.x / MT;          // 32 x 8
+    for (int r = ty; r < MT; r += VEC_THREADS / MT) t[r][tx] = M[(bi * MT + r) * ld + bj * MT + tx];
+    __syncthreads();
+    for (int r = ty; r < MT; r += VEC_THREADS / MT)
+        if (bi != bj || tx > r) M[(bj * MT + r) * ld + bi * MT + tx] = t[tx][r];
+}
+
+struct SoftVecs {          // each C x Np, class-major
+    double *a, *a_prev, *f, *f_prev, *s, *g, *b;
+};
+
+// One thread per point.  mode 0: F = A K from the tile partials; mode 1: the halved step, A <- (A + A_prev) / 2,
+// F <- (F + F_prev) / 2.  Then P = softmax over the classes, s = sqrt(P), g = Y - P, B = P o F - P o sum_c(P o F) + Y - P;
+// entries past N are 0.  psi_part[2 blk] = sum A o F, psi_part[2 blk + 1] = sum_i (F[label_i, i] - logsumexp_c F_ci).
+__global__ __launch_bounds__(VEC_THREADS) void softmax_newton_kernel(int mode, const double* __restrict__ part, int64_t nt,
+                                                                     int64_t N, int64_t Np, int C,
+                                                                     const double* __restrict__ y, SoftVecs v,
+                                                                     double* __restrict__ psi_part) {
+    __shared__ double sh[2 * (VEC_THREADS / 64)];
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    const int64_t pstride = nt * nt * LT;
+    double af = 0.0, lp = 0.0;
+    if (i < Np) {
+        double f[MAXC], pr[MAXC];
+        double fmx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            f[c] = 0.0; pr[c] = 0.0;
+            if (c < C) {
+                const int64_t o = c * Np + i;
+                double a;
+                if (mode == 0) {
+                    a = v.a[o];
+                    f[c] = i < N ? slot_sum(part + c * pstride, nt, i) : 0.0;
+                } else {
+                    a = (v.a[o] + v.a_prev[o]) / 2;
+                    f[c] = (v.f[o] + v.f_prev[o]) / 2;
+                    v.a[o] = a;
+                }
+                v.f[o] = f[c];
+                if (i < N) af = fma(a, f[c], af);
+                fmx = fmax(fmx, f[c]);
+            }
+        }
+        if (i < N) {
+            const int lab = (int)y[i];
+            double se = 0.0, spf = 0.0, flab = 0.0;
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) { pr[c] = exp(f[c] - fmx); se += pr[c]; }
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) {
+                    pr[c] = pr[c] / se;
+                    spf += pr[c] * f[c];
+                    if (c == lab) flab = f[c];
+                }
+            lp = flab - (fmx + log(se));
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) {
+                    const int64_t o = c * Np + i;
+                    const double yc = c == lab ? 1.0 : 0.0;
+                    v.s[o] = sqrt(pr[c]);
+                    v.g[o] = yc - pr[c];
+                    v.b[o] = ((pr[c] * f[c] - pr[c] * spf) + yc) - pr[c];
+                }
+        } else {
+            for (int c = 0; c < C; ++c) {
+                const int64_t o = c * Np + i;
+                v.s[o] = 0.0; v.g[o] = 0.0; v.b[o] = 0.0;
+            }
+        }
+    }
+    wg_reduce2(af, lp, sh);
+    if (threadIdx.x == 0) { psi_part[2 * blockIdx.x] = af; psi_part[2 * blockIdx.x + 1] = lp; }
+}
+
+// out[0] = Psi = -sum(A o F) / 2 + sum log p, out[1] = the Cholesky's first bad pivot (INT64_MAX: none) as a double,
+// out[2] = the backward solve's give-up word (0 without one)
+__global__ __launch_bounds__(VEC_THREADS) void softmax_psi_kernel(const double* __restrict__ psi_part, int64_t nblk,
+                                                                  const int64_t* __restrict__ info,
+                                                                  const int* __restrict__ flag, double* __restrict__ out) {
+    __shared__ double sh[2 * (VEC_THREADS / 64)];
+    double af = 0.0, lp = 0.0;
+    for (int64_t k = threadIdx.x; k < nblk; k += VEC_THREADS) { af += psi_part[2 * k]; lp += psi_part[2 * k + 1]; }
+    wg_reduce2(af, lp, sh);
+    if (threadIdx.x == 0) {
+        out[0] = -0.5 * af + lp;
+        out[1] = (double)*info;
+        out[2] = flag ? (double)*flag : 0.0;
+    }
+}
+
+// out_c[i] = sign * (tile partials of vector c summed), 0 past N; total (optional) = sum_c out_c[i] in index order
+__global__ __launch_bounds__(VEC_THREADS) void softmax_vec_kernel(const double* __restrict__ part, int64_t nt, int64_t N,
+                                                                  int64_t Np, int C, double sign, double* __restrict__ out,
+                                                                  double* __restrict__ total) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    const int64_t pstride = nt * nt * LT;
+    double t = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const double val = i < N ? sign * slot_sum(part + c * pstride, nt, i) : 0.0;
+        out[c * Np + i] = val;
+        t += val;
+    }
+    if (total) total[i] = t;
+}
+
+// A_prev <- A, F_prev <- F, A_c <- B_c - C_c + E_c t  (the partials hold -E_c t)
+__global__ __launch_bounds__(VEC_THREADS) void softmax_update_kernel(const double* __restrict__ part, int64_t nt, int64_t N,
+                                                                     int64_t Np, int C, const double* __restrict__ cc,
+                                                                     SoftVecs v) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    const int64_t pstride = nt * nt * LT;
+    for (int c = 0; c < C; ++c) {
+        const int64_t o = c * Np + i;
+        v.a_prev[o] = v.a[o];
+        v.f_prev[o] = v.f[o];
+        v.a[o] = i < N ? (v.b[o] - cc[o]) - slot_sum(part + c * pstride, nt, i) : 0.0;
+    }
+}
+
+// V[i][i] = s[i]
+__global__ __launch_bounds__(VEC_THREADS) void softmax_seed_kernel(double* __restrict__ V, int64_t ld, int64_t Np,
+                                                                   const double* __restrict__ s) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i < Np) V[i * ld + i] = s[i];
+}
+
+// One workgroup per row i of R: out[i * C + c] = sum_j R[i][j] Z_c[i][j] in a fixed order, Z_c[i] = Z + c * zc + i * zr
+__global__ __launch_bounds__(VEC_THREADS) void softmax_rowdot_kernel(const double* __restrict__ R, int64_t ld, int64_t ncols,
+                                                                     const double* __restrict__ Z, int64_t zc, int64_t zr,
+                                                                     int C, double* __restrict__ out) {
+    __shared__ double sh[2 * (VEC_THREADS / 64)];
+    const int64_t i = blockIdx.x;
+    const double* Rr = R + i * ld;
+    for (int c = 0; c < C; ++c) {
+        const double* z = Z + c * zc + i * zr;
+        double acc = 0.0, unused = 0.0;
+        for (int64_t j = 2 * threadIdx.x; j < ncols; j += 2 * VEC_THREADS) {
+            const d2 r = *reinterpret_cast<const d2*>(Rr + j);
+            const d2 zv = *reinterpret_cast<const d2*>(z + j);
+            acc = fma(r.x, zv.x, acc);
+            acc = fma(r.y, zv.y, acc);
+        }
+        wg_reduce2(acc, unused, sh);
+        if (threadIdx.x == 0) out[i * C + c] = acc;
+        __syncthreads();
+    }
+}
+
+// One workgroup per test point i: cov[i][c][e] = U_c[i] . U_e[i] (row c * np + i of U), + sig2 - dd[i][c] where c == e
+__global__ __launch_bounds__(VEC_THREADS) void softmax_gram_kernel(const double* __restrict__ U, int64_t ld, int64_t np,
+                                                                   int64_t ncols, int C, double sig2,
+                                                                   const double* __restrict__ dd, double* __restrict__ cov) {
+    __shared__ double sh[2 * (VEC_THREADS / 64)];
+    const int64_t i = blockIdx.x;
+    for (int c = 0; c < C; ++c)
+        for (int e = 0; e <= c; ++e) {
+            const double* uc = U + (c * np + i) * ld;
+            const double* ue = U + (e * np + i) * ld;
+            double acc = 0.0, unused = 0.0;
+            for (int64_t j = 2 * threadIdx.x; j < ncols; j += 2 * VEC_THREADS) {
+                const d2 a = *reinterpret_cast<const d2*>(uc + j);
+                const d2 b = *reinterpret_cast<const d2*>(ue + j);
+                acc = fma(a.x, b.x, acc);
+                acc = fma(a.y, b.y, acc);
+            }
+            wg_reduce2(acc, unused, sh);
+            if (threadIdx.x == 0) {
+                if (c == e) acc += sig2 - dd[i * C + c];
+                cov[(i * C + c) * C + e] = acc;
+                cov[(i * C + e) * C + c] = acc;
+            }
+            __syncthreads();
+        }
+}
+
+// One workgroup per test point: L = chol(cov[i]) (a pivot <= 0 becomes 0 with its column), then
+// prob[i][c] = (1 / S) sum_s softmax(mu[i] + L z_s)_c: every thread sums its samples s = t, t + 256, ..., the 256 partial
+// sums are added in thread order
+__global__ __launch_bounds__(VEC_THREADS) void softmax_sample_kernel(int C, int64_t S, const double* __restrict__ mu,
+                                                                     const double* __restrict__ cov,
+                                                                     const double* __restrict__ z, double* __restrict__ prob) {
+    __shared__ double L[MAXC][MAXC];
+    __shared__ double m[MAXC];
+    __shared__ double partial[VEC_THREADS][MAXC];
+    const int64_t i = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const double* Sg = cov + i * C * C;
+        for (int r = 0; r < C; ++r) {
+            m[r] = mu[i * C + r];
+            for (int k = 0; k < C; ++k) L[r][k] = 0.0;
+        }
+        for (int j = 0; j < C; ++j) {
+            double dj = Sg[j * C + j];
+            for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k];
+            if (!(dj > 0.0)) continue;                       // the column stays 0
+            const double piv = sqrt(dj);
+            L[j][j] = piv;
+            for (int r = j + 1; r < C; ++r) {
+                double t = Sg[r * C + j];
+                for (int k = 0; k < j; ++k) t -= L[r][k] * L[j][k];
+                L[r][j] = t / piv;
+            }
+        }
+    }
+    __syncthreads();
+    double acc[MAXC], gv[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) acc[c] = 0.0;
+    for (int64_t s = threadIdx.x; s < S; s += VEC_THREADS) {
+        const double* zs = z + s * C;
+        double mx = -INFINITY, se = 0.0;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) {
+                double t = m[c];
+                for (int k = 0; k <= c; ++k) t += L[c][k] * zs[k];
+                gv[c] = t;
+                mx = fmax(mx, t);
+            }
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) { gv[c] = exp(gv[c] - mx); se += gv[c]; }
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) acc[c] += gv[c] / se;
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) partial[threadIdx.x][c] = acc[c];
+    __syncthreads();
+    if ((int)threadIdx.x < C) {
+        double t = 0.0;
+        for (int k = 0; k < VEC_THREADS; ++k) t += partial[k][threadIdx.x];
+        prob[i * C + threadIdx.x] = t / (double)S;
+    }
+}
+
+unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
+
+// vectors per pass over a tile: the fewest passes with at most 4 vectors each, spread evenly
+int symv_chunk(int nvec) {
+    const int passes = (nvec + 3) / 4;
+    return (nvec + passes - 1) / passes;
+}
+
+hipError_t launch_symv(hipStream_t st, const SymvArgs& a, int nmat) {
+    const dim3 grid((unsigned)(a.nt * (a.nt + 1) / 2), (unsigned)nmat);
+    switch (symv_chunk(a.nvec)) {
+        case 1: hipLaunchKernelGGL(softmax_symv_kernel<1>, grid, dim3(SYMV_THREADS), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(softmax_symv_kernel<2>, grid, dim3(SYMV_THREADS), 0, st, a); break;
+        case 3: hipLaunchKernelGGL(softmax_symv_kernel<3>, grid, dim3(SYMV_THREADS), 0, st, a); break;
+        default: hipLaunchKernelGGL(softmax_symv_kernel<4>, grid, dim3(SYMV_THREADS), 0, st, a); break;
+    }
+    return hipGetLastError();
+}
+
+// Vectors of the softmax state in c->sm.  C x Np each: A, A_prev, F, F_prev, sqrt(P), Y - P, B, K B, C; then Np each: sum_c C_c
+// and 2 for the backward solve (its right-hand side, its solution); then the Psi partials, the read-back record and the
+// C + 1 pairs of launch_logdiag_sumsq.
+enum { SV_A, SV_AP, SV_F, SV_FP, SV_S, SV_G, SV_B, SV_KB, SV_CC, SV_MATS };
+enum { SW_CSUM, SW_X, SW_VECS = SW_X + 2 };
+
+}  // namespace
+
+int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
+                     int* converged, double* f_hat) {
+    if (!c->have_train) return fail_arg("gpmi_softmax_fit: no training set (call gpmi_set_train)");
+    if (c->kind != 0) return fail_arg("gpmi_softmax_fit: squared-exponential kernel only (gpmi_set_kernel kind 0)");
+    if (C < 2 || C > MAXC) return fail_arg("gpmi_softmax_fit: n_classes must lie in [2, GPMI_SOFTMAX_MAX_CLASSES]");
+    if (!(ell != 0.0) || !std::isfinite(ell) || !std::isfinite(sigma))
+        return fail_arg("gpmi_softmax_fit: ell must be non-zero and hyper-parameters finite");
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail_arg("gpmi_softmax_fit: tol must be finite and >= 0");
+    if (max_iter < 0) return fail_arg("gpmi_softmax_fit: max_iter must be >= 0");
+    hipStream_t st = c->stream;
+    const int64_t N = c->N;
+    {
+        std::vector<double> hy((size_t)N);
+        HIP_TRY(hipMemcpyAsync(hy.data(), c->y.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (double v : hy)
+            if (!(v >= 0.0 && v < (double)C && v == std::floor(v)))
+                return fail_arg("gpmi_softmax_fit: labels must be integers in [0, n_classes)");
+    }
+    // the softmax state replaces whatever was resident: no regression factor and no binary Laplace fit survives
+    c->have_factor = false;
+    c->have_laplace = false;
+    c->have_softmax = false;
+    c->v_in_A = false;
+    c->have_vinv = false;
+    c->have_vside = false;
+    c->have_v = false;
+    c->post_in_P = false;
+    int rc = ensure_train_buffers(c, 0, false);
+    if (rc) return rc;
+    c->sig2 = sigma * sigma;
+    c->coef = -.5 * (1 / (ell * ell));
+    c->sigma = sigma; c->ell = ell;
+    const int64_t Np = c->Np, nt = Np / TILE, ld = c->ldA;
+    const int64_t nblk = (Np + VEC_THREADS - 1) / VEC_THREADS;
+    const int64_t msize = Np * ld;                  // doubles of one N x N matrix
+    HIP_TRY(c->Kn.ensure((size_t)msize * 8));       // K
+    HIP_TRY(c->U.ensure((size_t)msize * 8));        // V_c = S_c L_c^-T
+    HIP_TRY(c->sm_E.ensure((size_t)C * msize * 8)); // -E_c
+    HIP_TRY(c->sm.ensure(((size_t)(SV_MATS * C + SW_VECS) * Np + 2 * nblk + 8 + 2 * (MAXC + 1)) * 8));
+    HIP_TRY(c->sm_part.ensure((size_t)C * nt * nt * TILE * 8));
+    double* Sm = c->sm.as<double>();
+    auto mat = [&](int k) { return Sm + (int64_t)k * C * Np; };
+    double* wv = Sm + (int64_t)SV_MATS * C * Np;
+    double* psi_part = wv + SW_VECS * Np;
+    double* rec = psi_part + 2 * nblk;
+    double* zrec = rec + 8;
+    const SoftVecs v{mat(SV_A), mat(SV_AP), mat(SV_F), mat(SV_FP), mat(SV_S), mat(SV_G), mat(SV_B)};
+    double* A = c->A.as<double>();
+    double* K = c->Kn.as<double>();
+    double* V = c->U.as<double>();
+    double* nE = c->sm_E.as<double>();
+    double* part = c->sm_part.as<double>();
+    const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
+    const bool chain = tuning().panel_fused && tuning().trsv_vinv >= 2;
+    if (chain) {                          // the give-up word is read from the first iteration on
+        HIP_TRY(c->flag.ensure(64));
+        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 64, st));
+    }
+    HIP_TRY(hipMemsetAsync(v.a, 0, (size_t)C * Np * 8, st));
+    const int64_t big = std::numeric_limits<int64_t>::max();
+    HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, st));
+
+    RbfArgs r;                            // K, once per fit
+    r.A = r.B = c->X.as<double>();
+    r.nA = r.nB = N; r.d = c->d; r.row0 = 0; r.nrows = Np; r.ncols = Np;
+    set_kernel_args(c, r);
+    r.diag_add = 0.0; r.symmetric = 1; r.delta_square = 1;
+    r.max_sq = box_max_sq(c->boxX, c->boxX);
+    r.out = K; r.ld = ld;
+    HIP_TRY(launch_rbf(st, r));
+
+    SymvArgs kx;                          // K times C vectors
+    kx.M = K; kx.mstride = 0; kx.ld = ld; kx.nt = nt; kx.xstride = 0; kx.nvec = C; kx.part = part;
+    SymvArgs ex;                          // -E_c times one vector each
+    ex.M = nE; ex.mstride = msize; ex.ld = ld; ex.nt = nt; ex.nvec = 1; ex.part = part;
+
+    double h[3];
+    auto evaluate = [&](int mode) -> int {
+        hipLaunchKernelGGL(softmax_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, st, mode, (const double*)part,
+                           nt, N, Np, C, (const double*)c->y.as<double>(), v, psi_part);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(softmax_psi_kernel, dim3(1), dim3(VEC_THREADS), 0, st, (const double*)psi_part, nblk,
+                           (const int64_t*)c->info.as<int64_t>(), (const int*)(chain ? c->flag.as<int>() : nullptr), rec);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, rec, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        c->timers_collect();
+        if (h[1] != (double)big) { g_err = "gpmi_softmax_fit: a Cholesky factorisation met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
+        if (h[2] != 0.0) return fail_runtime(hipErrorUnknown, "gpmi_softmax_fit: the single-launch backward solve gave up waiting for a block");
+        if (!std::isfinite(h[0])) return fail_arg("gpmi_softmax_fit: the objective is not finite");
+        return GPMI_OK;
+    };
+
+    double psi_prev = 0.0;
+    bool have_prev = false, conv = false;
+    int it = 0;
+    for (;;) {
+        kx.x = v.a;                                                   // 1. F = A K
+        HIP_TRY(launch_symv(st, kx, 1));
+        if ((rc = evaluate(0)) != GPMI_OK) return rc;
+        if (have_prev) {                                              // 2.
+            for (int halvings = 0;;) {
+                const double d = h[0] - psi_prev, thr = tol * std::max(1.0, std::fabs(h[0]));
+                if (std::fabs(d) <= thr) { conv = true; break; }
+                if (d < -thr && halvings < 20) {
+                    if ((rc = evaluate(1)) != GPMI_OK) return rc;
+                    ++halvings;
+                    continue;
+                }
+                break;
+            }
+        }
+        const bool last = conv || it >= max_iter;
+        // 3. per class: L_c = chol(I + s_c s_c^T o K) in A, V = S_c L_c^-T, -E_c = -V V^T (lower tiles)
+        HIP_TRY(launch_fill_rows(st, c->m_row(), ld, TILE, Np, 0.0));     // nothing rides in these factorisations
+        for (int k = 0; k < C; ++k) {
+            const double* sk = v.s + (int64_t)k * Np;
+            hipLaunchKernelGGL(softmax_bmat_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)K, A, ld, N, sk);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
+            c->have_vinv = c->have_vside = false;
+            c->factor_fused = tuning().panel_fused;
+            HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * k));
+            HIP_TRY(launch_fill_rows(st, V, ld, Np, Np, 0.0));
+            hipLaunchKernelGGL(softmax_seed_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, V, ld, Np, sk);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(solve_sweep(c, V, ld, Np, true));
+            double* Ek = nE + (int64_t)k * msize;
+            HIP_TRY(launch_fill_rows(st, Ek, ld, Np, Np, 0.0));
+            const int64_t NB = c->block(Np);
+            for (int64_t r0 = 0; r0 < Np; r0 += NB) {                 // row block r0 of V is zero left of column r0
+                const int64_t nb = std::min<int64_t>(NB, Np - r0);
+                GemmArgs g;
+                g.C = Ek + r0 * ld; g.A = V + r0 * ld + r0; g.B = V + r0;
+                g.ldc = g.lda = g.ldb = ld;
+                g.M = nb; g.N = r0 + nb; g.K = Np - r0;
+                g.mode = 0; g.lower = 1; g.diag_off = r0;
+                HIP_TRY(launch_gemm_nt(st, g));
+            }
+        }
+        if (!last) {                                                  // 4. c_c = E_c (K b_c), sum_c c_c rides with M
+            kx.x = v.b;
+            HIP_TRY(launch_symv(st, kx, 1));
+            hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N,
+                               Np, C, 1.0, mat(SV_KB), (double*)nullptr);
+            HIP_TRY(hipGetLastError());
+            ex.x = mat(SV_KB); ex.xstride = Np;
+            HIP_TRY(launch_symv(st, ex, C));
+            hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N,
+                               Np, C, -1.0, mat(SV_CC), wv + SW_CSUM * Np);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_set_yrow(st, c->m_row(), wv + SW_CSUM * Np, N, Np));
+        }
+        // 5. M = chol(sum_c E_c) in A
+        hipLaunchKernelGGL(softmax_esum_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)nE, msize, C, A, ld, N);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
+        c->have_vinv = c->have_vside = false;
+        c->factor_fused = tuning().panel_fused;
+        HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * C));
+        if (last) break;
+        double* x = wv + SW_X * Np;                                   // 6. t = M^-T M^-1 sum_c c_c, A <- B - C + [E_c t]
+        HIP_TRY(hipMemcpyAsync(x, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, st));
+        if (c->factor_fused) {
+            HIP_TRY(backward_solve_fused(c, x, x + Np));
+            x += Np;
+        } else {
+            HIP_TRY(launch_trsv_lt(st, A, ld, x, Np));
+        }
+        ex.x = x; ex.xstride = 0;
+        HIP_TRY(launch_symv(st, ex, C));
+        hipLaunchKernelGGL(softmax_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np,
+                           C, (const double*)mat(SV_CC), v);
+        HIP_TRY(hipGetLastError());
+        psi_prev = h[0];
+        have_prev = true;
+        ++it;
+    }
+    // prediction multiplies by the whole E_c
+    {
+        const int64_t nm = Np / MT;
+        hipLaunchKernelGGL(softmax_mirror_kernel, dim3((unsigned)(nm * (nm + 1) / 2), (unsigned)C), dim3(VEC_THREADS), 0, st,
+                           nE, msize, ld);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> red(2 * (size_t)(C + 1));
+    int64_t info = 0;
+    HIP_TRY(hipMemcpyAsync(red.data(), zrec, red.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, st));
+    if (f_hat)
+        HIP_TRY(hipMemcpy2DAsync(f_hat, (size_t)N * 8, v.f, (size_t)Np * 8, (size_t)N * 8, (size_t)C, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+    if (info != big) { g_err = "gpmi_softmax_fit: a Cholesky factorisation met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
+    // log q = Psi - sum_c sum log diag L_c - sum log diag M
+    double z = 0.0;
+    for (int k = 0; k < C; ++k) z += red[2 * (size_t)k];
+    if (log_q) *log_q = (h[0] - z) - red[2 * (size_t)C];
+    if (iters) *iters = it;
+    if (converged) *converged = conv ? 1 : 0;
+    c->sm_classes = C;
+    c->have_softmax = true;
+    return GPMI_OK;
+}
+
+int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const double* normals, double* prob) {
+    if (!c->have_softmax) return fail_arg("gpmi_softmax_predict: no softmax fit resident (call gpmi_softmax_fit)");
+    if (!c->have_test) return fail_arg("gpmi_softmax_predict: no test set (call gpmi_set_test)");
+    if (S < 0 || (S > 0 && (!normals || !prob))) return fail_arg("gpmi_softmax_predict: n_samples > 0 needs normals and prob");
+    Tuning tn = c->tune;
+    tn.panel_fused = c->factor_fused;      // solve with the kind of leaves that produced the resident factor
+    TuneScope tune_scope(&tn);
+    hipStream_t st = c->stream;
+    const int C = c->sm_classes;
+    const int64_t Np = c->Np, np_ = c->np_, n = c->n, ld = c->ldA, msize = Np * ld;
+    c->have_v = false;
+    c->v_in_A = false;
+    c->ldV = Np + c->ld_pad;
+    const int64_t ldV = c->ldV;
+    HIP_TRY(c->V.ensure((size_t)np_ * ldV * 8));
+    HIP_TRY(c->sm_B.ensure((size_t)C * np_ * ldV * 8));
+    HIP_TRY(c->sm_out.ensure(((size_t)np_ * C * (3 + C) + (size_t)S * C) * 8));
+    double* R = c->V.as<double>();
+    double* Bc = c->sm_B.as<double>();
+    double* o_mu = c->sm_out.as<double>();
+    double* o_dd = o_mu + np_ * C;
+    double* o_prob = o_dd + np_ * C;
+    double* o_cov = o_prob + np_ * C;
+    double* o_z = o_cov + np_ * C * C;
+    const double* G = c->sm.as<double>() + (int64_t)SV_G * C * Np;
+    const double* nE = c->sm_E.as<double>();
+
+    RbfArgs r;                            // R = K(X*, X)
+    r.A = c->Xs.as<double>(); r.B = c->X.as<double>();
+    r.nA = n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = Np;
+    set_kernel_args(c, r);
+    r.diag_add = 0.; r.symmetric = 0;
+    r.delta_square = (n == c->N) ? 1 : 0;
+    r.max_sq = box_max_sq(c->boxXs, c->boxX);
+    r.out = R; r.ld = ldV;
+    HIP_TRY(launch_rbf(st, r));
+    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,
+                       (int64_t)0, C, o_mu);                          // mu* = R (Y - P)^T
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_fill_rows(st, Bc, ldV, C * np_, Np, 0.0));
+    for (int k = 0; k < C; ++k) {                                     // B_c = R E_c = 0 - R (-E_c)^T
+        GemmArgs g;
+        g.C = Bc + (int64_t)k * np_ * ldV; g.A = R; g.B = nE + (int64_t)k * msize;
+        g.ldc = g.lda = ldV; g.ldb = ld;
+        g.M = np_; g.N = Np; g.K = Np;
+        g.mode = 0; g.lower = 0; g.diag_off = 0;
+        HIP_TRY(launch_gemm_nt(st, g));
+    }
+    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np,
+                       (const double*)Bc, np_ * ldV, ldV, C, o_dd);   // B_c[i] . R[i]
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(solve_sweep(c, Bc, ldV, C * np_));                        // U_c^T = B_c M^-T, all classes in one sweep
+    hipLaunchKernelGGL(softmax_gram_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)Bc, ldV, np_, Np, C,
+                       c->sig2, (const double*)o_dd, o_cov);
+    HIP_TRY(hipGetLastError());
+    if (S > 0) {
+        HIP_TRY(hipMemcpyAsync(o_z, normals, (size_t)S * C * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(softmax_sample_kernel, dim3((unsigned)n), dim3(VEC_THREADS), 0, st, C, S, (const double*)o_mu,
+                           (const double*)o_cov, (const double*)o_z, o_prob);
+        HIP_TRY(hipGetLastError());
+    }
+    if (mu) HIP_TRY(hipMemcpyAsync(mu, o_mu, (size_t)n * C * 8, hipMemcpyDeviceToHost, st));
+    if (cov) HIP_TRY(hipMemcpyAsync(cov, o_cov, (size_t)n * C * C * 8, hipMemcpyDeviceToHost, st));
+    if (S > 0) HIP_TRY(hipMemcpyAsync(prob, o_prob, (size_t)n * C * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+    return GPMI_OK;
+}
+
+}  // namespace gpmi

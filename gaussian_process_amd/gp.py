@@ -16,6 +16,23 @@ from . import _lib
 from ._lib import as_f64, check, ptr, scalar
 
 
+def softmax_labels(labels, n_classes=None):
+    """Host-side check of multi-class labels, before any device call: -> (labels as float64, n_classes).  Every label
+    must be an integer in [0, n_classes); n_classes (default: largest label + 1) must lie in
+    [2, GPMI_SOFTMAX_MAX_CLASSES]."""
+    lab = as_f64(labels, 1, "labels")
+    if lab.size == 0 or not np.all(np.isfinite(lab)) or np.any(lab != np.floor(lab)):
+        raise ValueError("labels must be integers in [0, n_classes)")
+    if n_classes is None:
+        n_classes = int(lab.max()) + 1
+    if n_classes != int(n_classes) or not 2 <= int(n_classes) <= _lib.SOFTMAX_MAX_CLASSES:
+        raise ValueError("n_classes must be an integer in [2, %d], got %r" % (_lib.SOFTMAX_MAX_CLASSES, n_classes))
+    n_classes = int(n_classes)
+    if lab.min() < 0 or lab.max() >= n_classes:
+        raise ValueError("labels must be integers in [0, n_classes = %d)" % n_classes)
+    return lab, n_classes
+
+
 class GPContext:
     """One GPU.  Not thread-safe: use one per thread."""
 
@@ -312,6 +329,49 @@ class GPContext:
         f_mean, f_var, prob = np.empty(self.n), np.empty(self.n), np.empty(self.n)
         check(self._lib.gpmi_laplace_predict_resident(self._h, ptr(f_mean), ptr(f_var), ptr(prob)))
         return f_mean, f_var, prob
+
+    # ---- multi-class classification (softmax Laplace approximation) ---------------------
+    def softmax_fit(self, X, labels, n_classes, sigma, l, *, tol=1e-10, max_iter=100):
+        """GPML Algorithm 3.3 (softmax likelihood) on the GPU for integer labels in [0, n_classes) and one
+        squared-exponential prior sigma**2 exp(-.5 sqdist / l**2) shared by the n_classes latent functions.  Returns
+        (log_q, F_hat, iters, converged): the Laplace approximation of the log marginal likelihood, the posterior mode
+        as an (n_classes, N) array, the Newton steps taken and whether |Psi - Psi_prev| <= tol max(1, |Psi|) was reached
+        (a RuntimeWarning when not).  Y - P, the matrices E_c and the factor of sum_c E_c stay on the device for
+        softmax_predict."""
+        import warnings
+        lab, n_classes = softmax_labels(labels, n_classes)
+        self.set_train(X, lab)
+        log_q = C.c_double()
+        iters, conv = C.c_int(), C.c_int()
+        f_hat = np.empty((n_classes, self.N))
+        st = self._lib.gpmi_softmax_fit(self._h, n_classes, scalar(sigma, "sigma"), scalar(l, "l"), float(tol),
+                                        int(max_iter), C.byref(log_q), C.byref(iters), C.byref(conv), ptr(f_hat))
+        check(st)
+        self.n_classes = n_classes
+        if not conv.value:
+            warnings.warn("softmax Laplace approximation: Newton iteration did not converge in %d steps (tol=%g)"
+                          % (iters.value, tol), RuntimeWarning, stacklevel=2)
+        return log_q.value, f_hat, iters.value, bool(conv.value)
+
+    def softmax_predict(self, Xs, normals=None):
+        """GPML Algorithm 3.4 on the resident softmax fit: (mu, cov, prob) at Xs -- the latent mean (n, C), the latent
+        covariance (n, C, C) and, when `normals` (S, C) standard normal draws are given, the class probabilities
+        (n, C) = mean over s of softmax(mu + chol(cov) normals[s]) (the same draws for every test point); prob is None
+        without them."""
+        self.set_test(Xs)
+        nc = int(getattr(self, "n_classes", 0))
+        if nc < 2:
+            raise ValueError("softmax_predict: no softmax fit resident (call softmax_fit)")
+        mu, cov = np.empty((self.n, nc)), np.empty((self.n, nc, nc))
+        S, z, prob = 0, None, None
+        if normals is not None:
+            z = as_f64(normals, 2, "normals")
+            if z.shape[0] < 1 or z.shape[1] != nc:
+                raise ValueError("normals must be (S, %d) with S >= 1, got %s" % (nc, z.shape))
+            S, prob = z.shape[0], np.empty((self.n, nc))
+        check(self._lib.gpmi_softmax_predict_resident(self._h, ptr(mu), ptr(cov), S, ptr(z) if S else None,
+                                                      ptr(prob) if S else None))
+        return mu, cov, prob
 
     # ---- batched LML ----------------------------------------------------------------
     def lml_batch(self, triples):

@@ -34,7 +34,7 @@ extern "C" {
 #define GPMI_ERR_BAD_ARG 2
 #define GPMI_ERR_RUNTIME 3
 
-#define GPMI_ABI_VERSION 3
+#define GPMI_ABI_VERSION 4
 
 /* stage timer slots filled by gpmi_get_timers (milliseconds, hipEvent-timed on
  * the context's compute stream; 0 when the stage did not run in the last call) */
@@ -233,6 +233,33 @@ int gpmi_laplace_fit(gpmi_ctx* ctx, double sigma, double ell, double tol, int ma
  *   prob = int expit(z) N(z | f_mean, f_var) dz     (composite trapezoid rule, error below 1e-12)
  * each n doubles or NULL. */
 int gpmi_laplace_predict_resident(gpmi_ctx* ctx, double* f_mean, double* f_var, double* prob);
+
+/* Multi-class GP classification by the Laplace approximation: GPML Algorithm 3.3 (Newton iteration for the mode, softmax
+ * likelihood, one latent function per class, all with the same squared-exponential prior K = sigma^2 exp(-.5 / l^2
+ * sqdist), no noise) and 3.4 (prediction), the working form of GP_multi_classification.py.  The labels are the y of
+ * gpmi_set_train: each an integer in [0, n_classes), else GPMI_ERR_BAD_ARG; 2 <= n_classes <= GPMI_SOFTMAX_MAX_CLASSES;
+ * kernel kind 0 only.  With Y the 0/1 encoding and F, A, P of shape C x N (latent values, a = K^-1 f, softmax
+ * probabilities), from A = 0 each iteration forms F = A K, P and
+ *   Psi = -1/2 sum(A o F) + sum(Y o F) - sum_i logsumexp_c F_ci,
+ * stops or halves the step by the rule of gpmi_laplace_fit, and otherwise factors L_c = chol(I + s_c s_c^T o K),
+ * s_c = sqrt(P_c), forms E_c = S_c L_c^-T L_c^-1 S_c and M = chol(sum_c E_c), and steps to
+ *   A <- B - [E_c K b_c]_c + [E_c M^-T M^-1 sum_c E_c K b_c]_c,   B = P o F - P o sum_c(P o F) + Y - P.
+ *   log_q = Psi - sum_c sum log diag L_c - sum log diag M   at the last iterate
+ * (the last term is missing from the printed Algorithm 3.3: 1/2 log|I + K W| = sum_c sum log diag L_c + sum log diag M).
+ * f_hat: C x N doubles (row c = latent values of class c) or NULL.  Y - P, the E_c and M stay resident in place of any
+ * regression factor or binary Laplace fit, under the rule stated at gpmi_laplace_fit.  Device memory: DESIGN.md. */
+#define GPMI_SOFTMAX_MAX_CLASSES 10
+int gpmi_softmax_fit(gpmi_ctx* ctx, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
+                     int* iters, int* converged, double* f_hat);
+/* Prediction on the resident test set (gpmi_set_test) from the resident softmax fit (Algorithm 3.4 with the shared
+ * kernel), R = K(X*, X):
+ *   mu (n x C) = R (Y - P)^T;  B_c = R E_c;  U_c = M^-1 B_c^T;
+ *   cov (n x C x C, or NULL): cov[i][c][c'] = U_c[:, i] . U_c'[:, i], plus sigma^2 - B_c[i] . R[i] where c == c'
+ *   prob (n x C): (1 / S) sum_s softmax(mu_i + chol(cov_i) z_s), with the S = n_samples rows of `normals` (S x C standard
+ *   normals supplied by the caller, the same for every test point: the result is a function of its inputs).  A pivot
+ *   <= 0 of the C x C Cholesky is set to 0 with its column.  n_samples 0: normals and prob NULL, no sampling. */
+int gpmi_softmax_predict_resident(gpmi_ctx* ctx, double* mu, double* cov, int64_t n_samples, const double* normals,
+                                  double* prob);
 
 int gpmi_get_timers(gpmi_ctx* ctx, double* stage_ms, int count);
 /* block the host until everything queued on the context has finished */
