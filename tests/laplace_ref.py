@@ -45,8 +45,9 @@ def newton_state(y, a, f):
     return dict(pi=pi, W=W, s=s, grad=grad, b=b, psi=psi)
 
 
-def laplace_fit(X, y, sigma, l, tol=1e-10, max_iter=100, K=None):
-    """-> dict(log_q, f, grad, s, L, iters, converged, K)"""
+def laplace_fit(X, y, sigma, l, tol=1e-10, max_iter=100, K=None, max_halvings=20):
+    """-> dict(log_q, f, grad, s, L, iters, converged, K, psi, halvings, decisions): halvings[k] is the number of
+    halved steps and decisions[k] the list of (d, thr) of every accept / halve decision taken after Newton step k + 1"""
     y = np.asarray(y, dtype=np.float64)
     K = rbf(X, X, sigma, l) if K is None else K                  # 1.
     N = y.shape[0]
@@ -54,18 +55,23 @@ def laplace_fit(X, y, sigma, l, tol=1e-10, max_iter=100, K=None):
     a_prev = f_prev = None
     psi_prev = None
     iters, converged = 0, False
+    halved, decisions = [], []
     while True:
         f = K @ a                                                # 2.
         st = newton_state(y, a, f)                               # 3.
         if psi_prev is not None:                                 # 4.
             halvings = 0
+            halved.append(0)
+            decisions.append([])
             while True:
                 d = st["psi"] - psi_prev
                 thr = tol * max(1.0, abs(st["psi"]))
+                halved[-1] = halvings
+                decisions[-1].append((d, thr))
                 if abs(d) <= thr:
                     converged = True
                     break
-                if d < -thr and halvings < 20:
+                if d < -thr and halvings < max_halvings:
                     a = (a + a_prev) / 2
                     f = (f + f_prev) / 2
                     st = newton_state(y, a, f)
@@ -84,7 +90,8 @@ def laplace_fit(X, y, sigma, l, tol=1e-10, max_iter=100, K=None):
         a = st["b"] - s * x
         iters += 1
     log_q = st["psi"] - np.log(np.diag(L)).sum()
-    return dict(log_q=log_q, f=f, grad=st["grad"], s=s, L=L, iters=iters, converged=converged, K=K, psi=st["psi"])
+    return dict(log_q=log_q, f=f, grad=st["grad"], s=s, L=L, iters=iters, converged=converged, K=K, psi=st["psi"],
+                halvings=halved, decisions=decisions)
 
 
 QUAD_T = 8.5

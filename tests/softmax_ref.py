@@ -32,8 +32,10 @@ def newton_state(Y, A, F):
     return P, psi
 
 
-def fit(X, labels, C, sigma, l, tol=1e-10, max_iter=100, K=None):
-    """-> dict(log_q, F, P, Y, G = Y - P, Es, M, psi, iters, converged, K)"""
+def fit(X, labels, C, sigma, l, tol=1e-10, max_iter=100, K=None, max_halvings=20):
+    """-> dict(log_q, F, P, Y, G = Y - P, Es, M, psi, iters, converged, K, halvings, decisions): halvings[k] is the
+    number of halved steps and decisions[k] the list of (d, thr) of every accept / halve decision taken after Newton
+    step k + 1"""
     K = rbf(X, X, sigma, l) if K is None else K
     labels = np.asarray(labels).astype(np.int64)
     N = labels.shape[0]
@@ -42,18 +44,23 @@ def fit(X, labels, C, sigma, l, tol=1e-10, max_iter=100, K=None):
     A = np.zeros((C, N))
     A_prev = F_prev = psi_prev = None
     iters, converged = 0, False
+    halved, decisions = [], []
     while True:
         F = A @ K                                                  # 1.
         P, psi = newton_state(Y, A, F)
         if psi_prev is not None:                                   # 2.
             halvings = 0
+            halved.append(0)
+            decisions.append([])
             while True:
                 d = psi - psi_prev
                 thr = tol * max(1.0, abs(psi))
+                halved[-1] = halvings
+                decisions[-1].append((d, thr))
                 if abs(d) <= thr:
                     converged = True
                     break
-                if d < -thr and halvings < 20:
+                if d < -thr and halvings < max_halvings:
                     A = (A + A_prev) / 2
                     F = (F + F_prev) / 2
                     P, psi = newton_state(Y, A, F)
@@ -80,7 +87,8 @@ def fit(X, labels, C, sigma, l, tol=1e-10, max_iter=100, K=None):
         A = B - Cc + np.stack([Es[c] @ t for c in range(C)])
         iters += 1
     log_q = psi - z - np.log(np.diag(M)).sum()
-    return dict(log_q=log_q, F=F, P=P, Y=Y, G=Y - P, Es=Es, M=M, psi=psi, iters=iters, converged=converged, K=K)
+    return dict(log_q=log_q, F=F, P=P, Y=Y, G=Y - P, Es=Es, M=M, psi=psi, iters=iters, converged=converged, K=K,
+                halvings=halved, decisions=decisions)
 
 
 def predict(ft, X, Xs, sigma, l):
