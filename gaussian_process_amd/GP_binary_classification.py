@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .gp import default_context
+from .gp import default_context, split_lengthscale
 
 
 def pi_function(f):
@@ -64,13 +64,15 @@ def laplace_fit(X_train, y_train, kernel_parameter=1, l=1, *, ctx=None, tol=1e-1
     :param X_train: (N, d) inputs
     :param y_train: (N,) labels, each exactly -1 or +1
     :param kernel_parameter: sigma of the RBF kernel sigma**2 exp(-.5 sqdist / l**2)
-    :param l: lengthscale
+    :param l: lengthscale; a d-vector gives every input dimension its own (set_lengthscales(l), common l = 1) and stays
+              set in ctx for the predictions; a scalar clears any the context carried
     :param ctx: a GPContext (default: this thread's context); the fit stays resident in it for predict_proba
     :return: (log_q, f_hat, iters, converged): approximate log marginal likelihood (GPML eq. 3.32), the mode, Newton
              steps taken, convergence flag (a RuntimeWarning is issued when False)
     """
     ctx = default_context() if ctx is None else ctx
-    return ctx.laplace_fit(X_train, y_train, kernel_parameter, l, tol=tol, max_iter=max_iter)
+    l, r = split_lengthscale(l)
+    return ctx.laplace_fit(X_train, y_train, kernel_parameter, l, tol=tol, max_iter=max_iter, lengthscales=r)
 
 
 def predict_latent(X_test, *, ctx=None):

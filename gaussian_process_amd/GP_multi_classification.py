@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .gp import default_context, softmax_labels
+from .gp import default_context, softmax_labels, split_lengthscale
 
 
 def softmax(X):
@@ -53,7 +53,8 @@ def laplace_fit(X_train, labels, kernel_parameter=1, l=1, *, n_classes=None, ctx
     :param X_train: (N, d) inputs
     :param labels: (N,) integer labels in [0, n_classes)
     :param kernel_parameter: sigma of the RBF kernel sigma**2 exp(-.5 sqdist / l**2), shared by all classes
-    :param l: lengthscale
+    :param l: lengthscale; a d-vector gives every input dimension its own (set_lengthscales(l), common l = 1) and stays
+              set in ctx for the predictions; a scalar clears any the context carried
     :param n_classes: C (default: largest label + 1); 2 <= C <= 10
     :param ctx: a GPContext (default: this thread's context); the fit stays resident in it for the predictions
     :return: (log_q, F_hat, iters, converged): approximate log marginal likelihood, the mode as a (C, N) array, Newton
@@ -61,7 +62,8 @@ def laplace_fit(X_train, labels, kernel_parameter=1, l=1, *, n_classes=None, ctx
     """
     labels, n_classes = softmax_labels(labels, n_classes)        # refused on the host, before any device call
     ctx = default_context() if ctx is None else ctx
-    return ctx.softmax_fit(X_train, labels, n_classes, kernel_parameter, l, tol=tol, max_iter=max_iter)
+    l, r = split_lengthscale(l)
+    return ctx.softmax_fit(X_train, labels, n_classes, kernel_parameter, l, tol=tol, max_iter=max_iter, lengthscales=r)
 
 
 def predict_latent(X_test, *, ctx=None):

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .gp import default_context
+from .gp import default_context, split_lengthscale
 
 NOISE_VAR = 0.0005      # GP_regression.py:120
 SIGMA_F = 1             # GP_regression.py:121
@@ -25,9 +25,13 @@ def RBF_kernel(a, b, sigma, l):
     :param a: (N, d) inputs
     :param b: (M, d) inputs
     :param sigma: output scale (the kernel is sigma**2 * exp(...))
-    :param l: lengthscale (scalar or 1-element array)
+    :param l: lengthscale (scalar or 1-element array), or a d-vector: one lengthscale per input dimension
     :return: (N, M) float64 covariance matrix
     """
+    l, r = split_lengthscale(l)
+    if r is not None:                   # both inputs scaled on the host, then the isotropic entry with l = 1
+        a = np.asarray(a, dtype=np.float64) / r
+        b = np.asarray(b, dtype=np.float64) / r
     return default_context().rbf(a, b, sigma, l)
 
 
@@ -85,6 +89,9 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
                noise_var=NOISE_VAR, jitter=POST_JITTER, return_lml=False, ctx=None, n_gpus=None, dist=None):
     """GP posterior at the test points, reference GP_regression.py:109-156.
 
+    With kernel_choice 'rbf', l may be a d-vector (d > 1): one lengthscale per input dimension.  A scalar or 1-element l
+    is the reference's isotropic kernel and clears any per-dimension lengthscales the context carried.
+
     :return: (mu_post (n,), stand_devi (n,), f_post_fun (n, num_fun)); with return_lml=True a
              fourth element, the log marginal likelihood of the fit (tune_hyperparms_regression.py:312
              -- not the discarded expression at GP_regression.py:151, which lacks the log)
@@ -92,7 +99,12 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
     would (K + sI at :138, posterior covariance at :154).  The normals of :155
     are drawn on the host from np.random in the reference's order.
     """
+    r = None
+    if kernel_choice == 'rbf':
+        l, r = split_lengthscale(l)     # a d-vector: one lengthscale per input dimension, common l = 1
     gp = _dist_of(n_gpus, dist)
+    if gp is not None and r is not None:
+        raise ValueError("per-dimension lengthscales (a vector l) are not available on the partitioned path (n_gpus / dist)")
     if gp is not None:
         # the covariance row-block partitioned over the ranks of the node (dist.py); every rank makes this call
         # with the same arguments and gets the same results; the normals of :155 come from each rank's own
@@ -115,12 +127,14 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
         # :126-128, 138-148 and 153-154 in one pass: ONE Cholesky of [[K + sI, .], [K(X*, X), K_ss + jitter I]] -- the test
         # rows ride through it below the training rows, and its last n columns are L_ (gpmi_fit_predict_sample_resident)
         lml, mu_post, stand_devi, _ = ctx.fit_predict_sample(X_train, y_train, X_test, sg, ll, noise_var, jitter, want_sd=True,
-                                                             want_factor=False)
+                                                             want_factor=False, lengthscales=r)
         n = mu_post.shape[0]
         normals = np.random.normal(size=(n, num_fun))          # :155, drawn on the host in the reference's order
         LZ = ctx.post_sample(jitter, normals)                  # L_ stays on the device: n x num_fun crosses PCIe, not n x n
     finally:
         ctx.set_kernel('rbf')
+        if r is not None:
+            ctx.set_lengthscales(None)  # like the kernel choice, the lengthscales of this call do not outlive it
     f_post_fun = mu_post.reshape(-1, 1) + LZ               # :155
     if return_lml:
         return mu_post, stand_devi, f_post_fun, np.float64(lml)

@@ -281,6 +281,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
         return fail_arg("gpmi_factorize: ell must be non-zero and hyper-parameters finite");
     if (std::isnan(noise_var)) return fail_arg("gpmi_factorize: noise_var is NaN");
     if (c->kind == 2 && c->d != 1) return fail_arg("gpmi_factorize: the periodic kernel is 1-D only (GP_regression.py:48)");
+    if (c->kind != 0 && c->ard()) return fail_arg("gpmi_factorize: per-dimension lengthscales need the squared-exponential kernel (kind 0)");
     // the test set's rows: inside the panel and update launches (1) or one block column behind on their own stream (2)
     int form = 0;
     if (with_test) {
@@ -317,11 +318,11 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
 
     size_t sp = c->span_begin(GPMI_T_KBUILD);
     RbfArgs r;
-    r.A = r.B = c->X.as<double>();
+    r.A = r.B = c->x_train();
     r.nA = r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = c->Np; r.ncols = c->Np;
     set_kernel_args(c, r);
     r.diag_add = noise_var; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->boxX, c->boxX);
+    r.max_sq = box_max_sq(c->box_train(), c->box_train());
     r.out = A; r.ld = c->ldA;
     HIP_TRY(launch_rbf(s, r));
     c->span_end(sp);                  // GPMI_T_KBUILD is the kernel-matrix build (a1 + a2) alone
@@ -334,21 +335,21 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (with_test) {                  // K(X*, X) below the y rows (a1 for K_s, GP_regression.py:127): they leave as v^T
         sp = c->span_begin(GPMI_T_KS);
         RbfArgs t;
-        t.A = c->Xs.as<double>(); t.B = c->X.as<double>();
+        t.A = c->x_test(); t.B = c->x_train();
         t.nA = c->n; t.nB = c->N; t.d = c->d; t.row0 = 0; t.nrows = c->np_; t.ncols = c->Np;
         set_kernel_args(c, t);
         t.diag_add = 0.; t.symmetric = 0;
         t.delta_square = (c->n == c->N) ? 1 : 0;
-        t.max_sq = box_max_sq(c->boxXs, c->boxX);
+        t.max_sq = box_max_sq(c->box_test(), c->box_train());
         t.out = Vr; t.ld = c->ldA;
         HIP_TRY(launch_rbf(s, t));
         if (form == 3) {              // K_ss + jitter I in the rows' own columns, lower tiles (GP_regression.py:128, 154)
             RbfArgs q;
-            q.A = q.B = c->Xs.as<double>();
+            q.A = q.B = c->x_test();
             q.nA = q.nB = c->n; q.d = c->d; q.row0 = 0; q.nrows = c->np_; q.ncols = c->np_;
             set_kernel_args(c, q);
             q.diag_add = jitter; q.symmetric = 1; q.delta_square = 1;
-            q.max_sq = box_max_sq(c->boxXs, c->boxXs);
+            q.max_sq = box_max_sq(c->box_test(), c->box_test());
             q.out = Vr + c->Np; q.ld = c->ldA;
             HIP_TRY(launch_rbf(s, q));
         }

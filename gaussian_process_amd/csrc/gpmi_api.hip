@@ -76,7 +76,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out})
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -307,8 +307,34 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->N = N; c->d = d;
     c->boxX.assign(X, N, d);
+    if (c->ard() && (int64_t)c->ard_r.size() != d) c->ard_r.clear();    // another d: back to isotropic
+    int rc = ard_rescale_train(c);
+    if (rc) return rc;
     c->have_train = true;
     return GPMI_OK;
+}
+
+int gpmi_set_lengthscales(gpmi_ctx* c, const double* r, int64_t d) {
+    if (!c) return fail_arg("gpmi_set_lengthscales: null context");
+    if (d < 0) return fail_arg("gpmi_set_lengthscales: d < 0");
+    if (r && d > 0) {
+        if (c->have_train && d != c->d) return fail_arg("gpmi_set_lengthscales: d differs from the resident training set's");
+        for (int64_t k = 0; k < d; ++k)
+            if (!std::isfinite(r[k]) || !(r[k] > 0.0)) return fail_arg("gpmi_set_lengthscales: every lengthscale must be finite and > 0");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // as a new training set: whatever was fitted belongs to the old covariance
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
+    c->post_in_A = c->post_in_P = false;
+    if (r && d > 0) c->ard_r.assign(r, r + d);
+    else c->ard_r.clear();
+    if (!c->ard()) return GPMI_OK;
+    HIP_TRY(c->ard_rdev.ensure((size_t)d * 8));
+    HIP_TRY(hipMemcpyAsync(c->ard_rdev.p, c->ard_r.data(), (size_t)d * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int rc = c->have_train ? ard_rescale_train(c) : GPMI_OK;
+    if (rc == GPMI_OK && c->have_train && c->have_test) rc = ard_rescale_test(c);
+    return rc;
 }
 
 int gpmi_factorize(gpmi_ctx* c, double sigma, double ell, double noise_var, double* lml,
@@ -362,6 +388,25 @@ int gpmi_get_factor_block(gpmi_ctx* c, int64_t r0, int64_t r1, int64_t c0, int64
 }
 
 }  // extern "C"
+
+// z = x / r for the training / test inputs of a context with per-dimension lengthscales (the raw inputs stay resident:
+// a tuner that changes r every iteration uploads d doubles, not N d)
+int gpmi::ard_rescale_train(gpmi_ctx* c) {
+    if (!c->ard()) return GPMI_OK;
+    HIP_TRY(c->Xz.ensure((size_t)c->N * c->d * 8));
+    HIP_TRY(launch_scale_inputs(c->stream, c->X.as<double>(), c->ard_rdev.as<double>(), c->N, c->d, c->Xz.as<double>()));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    box_scale(c->boxX, c->ard_r, c->boxZ);
+    return GPMI_OK;
+}
+int gpmi::ard_rescale_test(gpmi_ctx* c) {
+    if (!c->ard()) return GPMI_OK;
+    HIP_TRY(c->Xsz.ensure((size_t)c->n * c->d * 8));
+    HIP_TRY(launch_scale_inputs(c->stream, c->Xs.as<double>(), c->ard_rdev.as<double>(), c->n, c->d, c->Xsz.as<double>()));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    box_scale(c->boxXs, c->ard_r, c->boxZs);
+    return GPMI_OK;
+}
 
 // L^T x = b on the resident fused factor (a5): the first call after a factorisation inverts the 128 x 128 diagonal
 // blocks into their upper triangles (one launch, all blocks at once), every call then runs one product per block
@@ -430,6 +475,8 @@ int gpmi_set_test(gpmi_ctx* c, const double* Xs, int64_t n) {
     c->boxXs.assign(Xs, n, c->d);
     c->n = n;
     c->np_ = round_up(n, TILE);
+    int rc = ard_rescale_test(c);
+    if (rc) return rc;
     c->have_test = true;
     return GPMI_OK;
 }
@@ -453,12 +500,12 @@ int gpmi_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
 
     size_t sp = c->span_begin(GPMI_T_KS);
     RbfArgs r;
-    r.A = c->Xs.as<double>(); r.B = c->X.as<double>();
+    r.A = c->x_test(); r.B = c->x_train();
     r.nA = c->n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = c->np_; r.ncols = c->Np;
     set_kernel_args(c, r);
     r.diag_add = 0.; r.symmetric = 0;
     r.delta_square = (c->n == c->N) ? 1 : 0;   // kernel_4's delta is eye whenever the matrix is square (CO2_example.py:58)
-    r.max_sq = box_max_sq(c->boxXs, c->boxX);
+    r.max_sq = box_max_sq(c->box_test(), c->box_train());
     r.out = V; r.ld = c->ldV;
     HIP_TRY(launch_rbf(s, r));
     c->span_end(sp);
@@ -568,7 +615,7 @@ int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
         HIP_TRY(launch_gemm_nt(s, g));
     }
     GradArgs a;
-    a.A = a.B = c->X.as<double>(); a.nA = a.nB = c->N; a.d = c->d;
+    a.A = a.B = c->x_train(); a.nA = a.nB = c->N; a.d = c->d;
     a.row0 = 0; a.nrows = c->N;
     a.alpha_r = a.alpha_c = alpha;
     a.Kinv = Kn; a.ld = ld; a.kinv_sign = -1.0;
@@ -592,6 +639,79 @@ int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     for (int64_t b = 0; b < nblk; ++b) { sl += part[2 * b]; ss += part[2 * b + 1]; }   // fixed order
     *d_ell = .5 * sl;
     *d_sigma = .5 * ss;
+    return GPMI_OK;
+}
+
+// The gradient with one lengthscale per input dimension, the output scale and the noise: d + 3 traces of the same
+// W = alpha alpha^T - K_y^-1 in one fused pass (grad.hip, the ARD kernel).  alpha, U and -K_y^-1 are formed exactly as in
+// gpmi_lml_grad; the per-block partials are summed on the device in a fixed order (at N = 65536 they are tens of MB).
+int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise) {
+    if (!c) return fail_arg("gpmi_lml_grad_ard: null context");
+    if (!c->have_factor) return fail_arg("gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)");
+    if (c->kind != 0) return fail_arg("gpmi_lml_grad_ard: squared-exponential kernel only");
+    HIP_TRY(hipSetDevice(c->device));
+    Tuning tn = c->tune;
+    tn.panel_fused = c->factor_fused;
+    TuneScope tune_scope(&tn);
+    hipStream_t s = c->stream;
+    const int64_t Np = c->Np, ld = c->ldA;
+    c->timers_reset({GPMI_T_GRAD});
+    HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
+    HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
+    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
+    size_t sp = c->span_begin(GPMI_T_GRAD);
+    double* alpha = c->vec.as<double>();
+    HIP_TRY(hipMemcpyAsync(alpha, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
+    if (c->factor_fused) {
+        HIP_TRY(backward_solve_fused(c, alpha, alpha + Np));
+        alpha += Np;
+    } else {
+        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), ld, alpha, Np));
+    }
+    double* U = c->U.as<double>();
+    HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
+    HIP_TRY(launch_set_identity_diag(s, U, ld, Np));
+    HIP_TRY(solve_sweep(c, U, ld, Np, true));
+    double* Kn = c->Kn.as<double>();
+    HIP_TRY(launch_fill_rows(s, Kn, ld, Np, Np, 0.0));
+    const int64_t NB = c->block(Np);
+    for (int64_t r0 = 0; r0 < Np; r0 += NB) {
+        const int64_t nb = std::min<int64_t>(NB, Np - r0);
+        GemmArgs g;
+        g.C = Kn + r0 * ld; g.A = U + r0 * ld + r0; g.B = U + r0;
+        g.ldc = g.lda = g.ldb = ld;
+        g.M = nb; g.N = r0 + nb; g.K = Np - r0;
+        g.mode = 0; g.lower = 1; g.diag_off = r0;
+        HIP_TRY(launch_gemm_nt(s, g));
+    }
+    GradArdArgs a;
+    a.Z = c->x_train(); a.n = c->N; a.d = c->d;
+    a.alpha = alpha; a.Kn = Kn; a.ld = ld; a.coef = c->coef;
+    const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
+    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
+    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
+    a.partial = c->gpart.as<double>();
+    a.sums = c->gsum.as<double>();
+    HIP_TRY(launch_grad_ard(s, a));
+    c->span_end(sp);
+    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
+    HIP_TRY(hipMemcpyAsync(sums.data(), a.sums, sums.size() * 8, hipMemcpyDeviceToHost, s));
+    int gave_up = 0;
+    if (c->factor_fused && tuning().trsv_vinv >= 2)
+        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c->timers_collect();
+    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_lml_grad_ard: the single-launch backward solve gave up waiting for a block");
+    // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums
+    const double l2 = c->ell * c->ell;
+    if (d_r)
+        for (int64_t k = 0; k < c->d; ++k) {
+            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
+            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
+        }
+    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
+    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
+    if (d_noise) *d_noise = .5 * sums[(size_t)w + 2];
     return GPMI_OK;
 }
 
@@ -677,11 +797,11 @@ static int post_factor_device(gpmi_ctx* c, double jitter, const double** factor,
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, s));
     size_t sp = c->span_begin(GPMI_T_POSTCHOL);
     RbfArgs r;   // K_ss + jitter*I, lower tiles (GP_regression.py:128,154)
-    r.A = r.B = c->Xs.as<double>();
+    r.A = r.B = c->x_test();
     r.nA = r.nB = n; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = np_;
     set_kernel_args(c, r);
     r.diag_add = jitter; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->boxXs, c->boxXs);
+    r.max_sq = box_max_sq(c->box_test(), c->box_test());
     r.out = P; r.ld = c->ldP;
     HIP_TRY(launch_rbf(s, r));
     GemmArgs g;  // P -= v^T v  (rows of V are the columns of v)
@@ -760,10 +880,10 @@ static int lane_prepare(gpmi_ctx* c, gpmi_ctx* l) {
     l->tune = c->tune;
     l->kind = c->kind; l->kp0 = c->kp0; l->kp1 = c->kp1;
     for (int i = 0; i < 11; ++i) l->kpv[i] = c->kpv[i];
-    l->N = c->N; l->d = c->d; l->boxX = c->boxX;
+    l->N = c->N; l->d = c->d; l->boxX = c->box_train();    // a lane is isotropic on the parent's (scaled) inputs
     HIP_TRY(l->X.ensure((size_t)c->N * c->d * 8));
     HIP_TRY(l->y.ensure((size_t)c->N * 8));
-    HIP_TRY(hipMemcpyAsync(l->X.p, c->X.p, (size_t)c->N * c->d * 8, hipMemcpyDeviceToDevice, l->stream));
+    HIP_TRY(hipMemcpyAsync(l->X.p, c->x_train(), (size_t)c->N * c->d * 8, hipMemcpyDeviceToDevice, l->stream));
     HIP_TRY(hipMemcpyAsync(l->y.p, c->y.p, (size_t)c->N * 8, hipMemcpyDeviceToDevice, l->stream));
     HIP_TRY(hipStreamSynchronize(l->stream));
     l->have_train = true;

@@ -72,6 +72,16 @@ struct Box {
         valid = finite;
     }
 };
+// The box of z = x / r from the box of x: division by a positive number is monotone under rounding, so the same
+// division the device performs on every element gives exact bounds of the scaled set.
+inline void box_scale(const Box& raw, const std::vector<double>& r, Box& out) {
+    out = raw;
+    if (raw.lo.size() != r.size()) { out.valid = false; return; }
+    for (size_t k = 0; k < r.size(); ++k) {
+        out.lo[k] = raw.lo[k] / r[k];
+        out.hi[k] = raw.hi[k] / r[k];
+    }
+}
 inline double box_max_sq(const Box& a, const Box& b) {
     if (!a.valid || !b.valid || a.lo.size() != b.lo.size()) return -1.0;
     double s = 0.0;
@@ -145,12 +155,25 @@ struct gpmi_ctx {
     uint64_t v_gen = 0, post_gen_P = 0;
     std::vector<double> hXs; // host copy of the test inputs (diag(K_ss) of the linear kernel)
     Box boxX, boxXs;         // bounding boxes of the training / test inputs
+    // Per-dimension relative lengthscales r_k (gpmi_set_lengthscales; empty: isotropic).  X and Xs keep the raw inputs;
+    // Xz and Xsz hold z = x / r, one IEEE division per element on the device, with boxZ / boxZs their boxes.  Every
+    // kernel-matrix build and the gradient read the inputs through x_train() / x_test() / box_train() / box_test(), so
+    // an isotropic context reads the buffers it always read.
+    std::vector<double> ard_r;
+    DevBuf Xz, Xsz, ard_rdev;
+    Box boxZ, boxZs;
+    bool ard() const { return !ard_r.empty(); }
+    const double* x_train() const { return ard() ? Xz.as<double>() : X.as<double>(); }
+    const double* x_test() const { return ard() ? Xsz.as<double>() : Xs.as<double>(); }
+    const Box& box_train() const { return ard() ? boxZ : boxX; }
+    const Box& box_test() const { return ard() ? boxZs : boxXs; }
     DevBuf Xs, V, P, vec, dense;
     DevBuf flag;             // one int the single-launch backward solve sets if a poll gave up
     DevBuf vside;            // Np x 128: the inverses of the 128 x 128 diagonal blocks, row-major (launch_vinv128's side buffer)
     bool have_vside = false; // vside matches the resident factor
     DevBuf cov_a, cov_b, cov_out;   // gpmi_rbf / gpmi_cov staging, kept across calls (the BO loops call them hundreds of times)
     DevBuf U, Kn, gpart;     // f2: L^-T, -(K+sI)^-1, per-tile partial sums of the gradient trace
+    DevBuf gsum;             // gpmi_lml_grad_ard: the d + 3 sums, reduced on the device
     double sigma = 1.0, ell = 1.0;   // hyper-parameters of the resident factorisation
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
@@ -243,6 +266,9 @@ int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows = 0, bool test_cols = fa
 int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, double* lml, int64_t* bad_pivot,
                    bool with_test = false, double* mu = nullptr, double* out2 = nullptr, int want_sd = 1,
                    bool with_post = false, double jitter = 0.0);
+// gpmi_api.hip: regenerate the scaled copy of the training / test inputs and its box (no-ops on an isotropic context)
+int ard_rescale_train(gpmi_ctx* c);
+int ard_rescale_test(gpmi_ctx* c);
 void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, double* out2, int want_sd);
 // gpmi_api.hip: L^T x = b on the resident fused factor (a5; the first call after a factorisation inverts its diagonal blocks)
 hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout);

@@ -162,6 +162,26 @@ struct GradArgs {
 };
 int64_t grad_trace_blocks(const GradArgs& a);
 hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a);
+// The same W against d + 3 derivatives (per-dimension lengthscales, l, sigma, noise) over the lower 128 x 128 tiles of
+// Kn = -K_y^-1: per launch `width` dimensions (4 / 8 / 16 / 32, zero differences beyond d) and, in the first launch, the
+// three others; d > 32 takes ceil(d / 32) launches.  sums[q * (width + 3) + j]: launch q's plain sums, without the
+// factors sigma^2 / (l^2 r_k) etc. (the caller's), each the fixed-order sum of the per-block partials.
+struct GradArdArgs {
+    const double* Z;          // scaled inputs n x d (device)
+    int64_t n, d;
+    const double* alpha;      // length n
+    const double* Kn;         // -K_y^-1, lower tiles valid, leading dimension ld
+    int64_t ld;
+    double coef;              // -1 / (2 l^2)
+    double* partial;          // (width + 3) * grad_ard_blocks doubles, component-major
+    double* sums;             // (width + 3) * grad_ard_launches doubles
+};
+int64_t grad_ard_blocks(const GradArdArgs& a);
+int64_t grad_ard_width(const GradArdArgs& a);
+int64_t grad_ard_launches(const GradArdArgs& a);
+hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a);
+// Z[i][k] = X[i][k] / r[k]: one IEEE division per element
+hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z);
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n);
 
 // ---- solve.hip -------------------------------------------------------------

@@ -135,6 +135,147 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
     }
 }
 
+// ---- d + 3 traces: per-dimension lengthscales (ARD), l, sigma, noise ---------------------------------------------
+// A sibling of grad_trace_kernel over the lower tiles of Kn = -K_y^-1 (the same tile enumeration, LDS staging
+// and rows per thread; the thread's two columns lie 64 apart so that a wave reads both edges densely), so that gpmi_lml_grad keeps its bits.  Per element: e_k^2 = (z_ik - z_jk)^2 for the DC dimensions of this
+// launch (zero beyond d), x = exp(coef * sum over ALL d of e_k^2), then
+//     acc_k += w x e_k^2,   acc_l += w x sq,   acc_s += w x,   acc_n += w on the diagonal
+// with w = alpha_i alpha_j - K_y^-1_ij, strictly-lower elements counted twice.  The accumulators are indexed by
+// compile-time constants only (every loop over them is unrolled), so they live in registers.  Block partials go out
+// component-major (partial[j * nblk + block]) and are summed by ard_reduce_kernel in a fixed order.
+struct ArdDev {
+    const double* Z;
+    int64_t n;
+    int d, k0;              // this launch covers dimensions k0 .. k0 + DC
+    const double* alpha;
+    const double* Kn;
+    int64_t ld;
+    double coef;
+    double* partial;
+    int64_t nblk;
+};
+
+template <int DC, bool LDS>
+__global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red[4][DC + 3];
+    const int s = blockIdx.x;
+    int ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
+    while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
+    while (ti * (ti + 1) / 2 > s) --ti;
+    const int tj = s - ti * (ti + 1) / 2;
+    const int d = p.d;
+    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
+    const int tid = threadIdx.x;
+    double* As = lds;               // [RT][DC]
+    double* Bs = lds + RT * DC;     // [DC][RT]
+    if (LDS) {                      // d <= DC, k0 == 0: dimensions d .. DC are zero on both edges
+        for (int e = tid; e < RT * DC; e += 256) {
+            const int r = e / DC, k = e - r * DC;
+            const int64_t ga = grow0 + r, gb = gcol0 + r;
+            As[r * DC + k] = (k < d && ga < p.n) ? p.Z[ga * d + k] : 0.0;
+            Bs[k * RT + r] = (k < d && gb < p.n) ? p.Z[gb * d + k] : 0.0;
+        }
+        __syncthreads();
+    }
+    const int cp = tid & 63, rg = tid >> 6;
+    const int64_t gc = gcol0 + cp;      // the thread's columns: gc and gc + 64 (dense LDS and Kn reads across the wave)
+    double acc[DC];
+#pragma unroll
+    for (int k = 0; k < DC; ++k) acc[k] = 0.0;
+    double acc_l = 0.0, acc_s = 0.0, acc_n = 0.0;
+    for (int r = 0; r < 32; ++r) {
+        const int lr = 32 * rg + r;
+        const int64_t gr = grow0 + lr;
+        if (gr >= p.n) break;                                    // wave-uniform
+        const double ar_ = p.alpha[gr];
+        const double* kp = p.Kn + gr * p.ld + gc;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {                            // the thread's two columns, one after the other
+            const int64_t g = gc + 64 * c;
+            const bool in = g < p.n;
+            double e2[DC];
+            double sq = 0.0;
+            if (LDS) {
+                const double* ar = &As[lr * DC];
+                const double* bc = &Bs[cp + 64 * c];
+#pragma unroll
+                for (int k = 0; k < DC; ++k) {
+                    const double e = ar[k] - bc[k * RT];
+                    e2[k] = e * e;
+                    sq += e2[k];
+                }
+            } else {
+                const double* ar = p.Z + gr * d;
+                const double* b = p.Z + (in ? g : 0) * d;
+#pragma unroll
+                for (int k = 0; k < DC; ++k) {
+                    const int kk = p.k0 + k;
+                    const double e = (kk < d) ? ar[kk] - b[kk] : 0.0;
+                    e2[k] = e * e;
+                    sq += e2[k];
+                }
+                for (int kk = 0; kk < p.k0; ++kk) {
+                    const double e = ar[kk] - b[kk];
+                    sq = fma(e, e, sq);
+                }
+                for (int kk = p.k0 + DC; kk < d; ++kk) {
+                    const double e = ar[kk] - b[kk];
+                    sq = fma(e, e, sq);
+                }
+            }
+            // Kn holds -K_y^-1, valid on and below the diagonal only
+            double w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
+            if (g == gr) acc_n += w;
+            else w += w;
+            const double wx = w * exp(p.coef * sq);
+#pragma unroll
+            for (int k = 0; k < DC; ++k) acc[k] = fma(wx, e2[k], acc[k]);
+            acc_l = fma(wx, sq, acc_l);
+            acc_s += wx;
+        }
+    }
+    // 64 lanes by a butterfly, then the four waves in order: the same order every run
+    const int wave = tid >> 6;
+    auto wave_sum = [](double v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        return v;
+    };
+#pragma unroll
+    for (int k = 0; k < DC; ++k) {
+        const double v = wave_sum(acc[k]);
+        if (cp == 0) red[wave][k] = v;
+    }
+    {
+        const double vl = wave_sum(acc_l), vs = wave_sum(acc_s), vn = wave_sum(acc_n);
+        if (cp == 0) { red[wave][DC] = vl; red[wave][DC + 1] = vs; red[wave][DC + 2] = vn; }
+    }
+    __syncthreads();
+    if (tid < DC + 3)
+        p.partial[(int64_t)tid * p.nblk + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// out[j] = sum over the blocks of partial[j * nblk + b]: thread t adds blocks t, t + 256, ... in order, then a fixed tree
+__global__ __launch_bounds__(256) void ard_reduce_kernel(const double* partial, int64_t nblk, double* out) {
+    __shared__ double sh[256];
+    const double* in = partial + (int64_t)blockIdx.x * nblk;
+    double v = 0.0;
+    for (int64_t b = threadIdx.x; b < nblk; b += 256) v += in[b];
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+}
+
+__global__ void scale_inputs_kernel(const double* X, const double* r, int64_t total, int d, double* Z) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) Z[i] = X[i] / r[i % d];
+}
+
 __global__ void set_identity_kernel(double* V, int64_t ld, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) V[i * ld + i] = 1.0;
@@ -146,6 +287,48 @@ hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(set_identity_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, ld, n);
     return hipGetLastError();
+}
+
+hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z) {
+    const int64_t total = n * d;
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scale_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, X, r, total, (int)d, Z);
+    return hipGetLastError();
+}
+
+int64_t grad_ard_blocks(const GradArdArgs& a) {
+    const int64_t T = (a.n + RT - 1) / RT;
+    return T * (T + 1) / 2;
+}
+// dimensions per launch: the narrowest of 4 / 8 / 16 / 32 that holds d, 32 beyond
+int64_t grad_ard_width(const GradArdArgs& a) { return a.d <= 4 ? 4 : a.d <= 8 ? 8 : a.d <= 16 ? 16 : 32; }
+int64_t grad_ard_launches(const GradArdArgs& a) { return a.d <= GRAD_MAXD ? 1 : (a.d + GRAD_MAXD - 1) / GRAD_MAXD; }
+
+template <int DC>
+static void grad_ard_go(hipStream_t s, const ArdDev& p) {
+    hipLaunchKernelGGL((grad_ard_kernel<DC, true>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
+}
+
+hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
+    if (a.n <= 0 || a.d <= 0) return hipSuccess;
+    ArdDev p;
+    p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld; p.coef = a.coef;
+    p.partial = a.partial; p.nblk = grad_ard_blocks(a);
+    const int w = (int)grad_ard_width(a);
+    const int64_t nl = grad_ard_launches(a);
+    for (int64_t q = 0; q < nl; ++q) {       // d > 32: every launch recomputes the whole squared distance and reads Kn again
+        p.k0 = (int)(q * GRAD_MAXD);
+        if (a.d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
+        else if (w == 4) grad_ard_go<4>(s, p);
+        else if (w == 8) grad_ard_go<8>(s, p);
+        else if (w == 16) grad_ard_go<16>(s, p);
+        else grad_ard_go<32>(s, p);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(ard_reduce_kernel, dim3((unsigned)(w + 3)), dim3(256), 0, s, a.partial, p.nblk, a.sums + q * (w + 3));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 int64_t grad_trace_blocks(const GradArgs& a) {

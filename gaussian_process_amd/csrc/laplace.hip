@@ -357,11 +357,11 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, st));
 
     RbfArgs r;
-    r.A = r.B = c->X.as<double>();
+    r.A = r.B = c->x_train();
     r.nA = r.nB = N; r.d = c->d; r.row0 = 0; r.nrows = Np; r.ncols = Np;
     set_kernel_args(c, r);
     r.diag_add = 0.0; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->boxX, c->boxX);
+    r.max_sq = box_max_sq(c->box_train(), c->box_train());
     r.out = A; r.ld = c->ldA;
 
     // Psi of the current iterate, with the previous Cholesky's pivot word and backward solve's give-up word
@@ -460,12 +460,12 @@ int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* pro
     const double* s = c->lap.as<double>() + LV_S * Np;
 
     RbfArgs r;                            // R = K(X*, X)
-    r.A = c->Xs.as<double>(); r.B = c->X.as<double>();
+    r.A = c->x_test(); r.B = c->x_train();
     r.nA = n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = Np;
     set_kernel_args(c, r);
     r.diag_add = 0.; r.symmetric = 0;
     r.delta_square = (n == c->N) ? 1 : 0;
-    r.max_sq = box_max_sq(c->boxXs, c->boxX);
+    r.max_sq = box_max_sq(c->box_test(), c->box_train());
     r.out = V; r.ld = c->ldV;
     HIP_TRY(launch_rbf(st, r));
     hipLaunchKernelGGL(laplace_rows_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, V, c->ldV, Np, grad, s, o);

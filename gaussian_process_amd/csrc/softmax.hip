@@ -533,11 +533,11 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, st));
 
     RbfArgs r;                            // K, once per fit
-    r.A = r.B = c->X.as<double>();
+    r.A = r.B = c->x_train();
     r.nA = r.nB = N; r.d = c->d; r.row0 = 0; r.nrows = Np; r.ncols = Np;
     set_kernel_args(c, r);
     r.diag_add = 0.0; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->boxX, c->boxX);
+    r.max_sq = box_max_sq(c->box_train(), c->box_train());
     r.out = K; r.ld = ld;
     HIP_TRY(launch_rbf(st, r));
 
@@ -703,12 +703,12 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     const double* nE = c->sm_E.as<double>();
 
     RbfArgs r;                            // R = K(X*, X)
-    r.A = c->Xs.as<double>(); r.B = c->X.as<double>();
+    r.A = c->x_test(); r.B = c->x_train();
     r.nA = n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = Np;
     set_kernel_args(c, r);
     r.diag_add = 0.; r.symmetric = 0;
     r.delta_square = (n == c->N) ? 1 : 0;
-    r.max_sq = box_max_sq(c->boxXs, c->boxX);
+    r.max_sq = box_max_sq(c->box_test(), c->box_train());
     r.out = R; r.ld = ldV;
     HIP_TRY(launch_rbf(st, r));
     hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,

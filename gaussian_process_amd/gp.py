@@ -33,6 +33,22 @@ def softmax_labels(labels, n_classes=None):
     return lab, n_classes
 
 
+KEEP = object()      # lengthscales=KEEP: leave the context's per-dimension lengthscales as they are
+
+
+def split_lengthscale(l):
+    """A lengthscale argument of the drop-in functions -> (common l, relative lengthscales or None).  A scalar, or the
+    1-element array the reference passes, is isotropic: (l, None).  A d-vector (d > 1) is one lengthscale per input
+    dimension: (1.0, vector)."""
+    a = np.asarray(l, dtype=np.float64)
+    if a.size == 1:
+        return l, None
+    if a.ndim != 1:
+        raise ValueError("l must be a scalar or a vector with one lengthscale per input dimension, got shape %s"
+                         % (a.shape,))
+    return 1.0, a
+
+
 class GPContext:
     """One GPU.  Not thread-safe: use one per thread."""
 
@@ -169,6 +185,27 @@ class GPContext:
         check(self._lib.gpmi_set_train(self._h, ptr(X), X.shape[0], X.shape[1], ptr(y)))
         self.N, self.d = X.shape
 
+    def _set_train_ard(self, X, y, lengthscales):
+        """set_train with the lengthscales= keyword of the fitting calls: None clears them (before the upload, so that an
+        isotropic call launches what it always launched), a vector sets them for the new training set."""
+        if lengthscales is None:
+            self.set_lengthscales(None)
+        self.set_train(X, y)
+        if lengthscales is not None and lengthscales is not KEEP:
+            self.set_lengthscales(lengthscales)
+
+    def set_lengthscales(self, r):
+        """Relative per-dimension lengthscales r_k > 0 (ARD): from now on this context's squared-exponential covariance
+        is sigma**2 exp(-.5 / l**2 * sum_k ((x_ik - x_jk) / r_k)**2) in every fit, prediction and gradient.  None
+        returns it to the isotropic state.  Whatever was fitted is dropped; the inputs stay on the device."""
+        if r is None:
+            check(self._lib.gpmi_set_lengthscales(self._h, None, 0))
+            return
+        r = as_f64(np.asarray(r, dtype=np.float64).reshape(-1), 1, "lengthscales")
+        if r.size == 0:
+            raise ValueError("lengthscales must not be empty (None clears them)")
+        check(self._lib.gpmi_set_lengthscales(self._h, ptr(r), r.shape[0]))
+
     def factorize(self, sigma, l, noise_var):
         """K + s I -> L, m = L^-1 y; returns the log-marginal-likelihood."""
         lml = C.c_double()
@@ -178,8 +215,8 @@ class GPContext:
         check(st, bad.value)
         return lml.value
 
-    def fit(self, X, y, sigma, l, noise_var):
-        self.set_train(X, y)
+    def fit(self, X, y, sigma, l, noise_var, *, lengthscales=KEEP):
+        self._set_train_ard(X, y, lengthscales)
         return self.factorize(sigma, l, noise_var)
 
     def alpha(self):
@@ -249,13 +286,14 @@ class GPContext:
         check(st, bad.value)
         return lml.value, mu, o2, L_
 
-    def fit_predict_sample(self, X, y, Xs, sigma, l, noise_var, jitter, want_sd=True, want_factor=True):
-        self.set_train(X, y)
+    def fit_predict_sample(self, X, y, Xs, sigma, l, noise_var, jitter, want_sd=True, want_factor=True, *,
+                           lengthscales=KEEP):
+        self._set_train_ard(X, y, lengthscales)
         self.set_test(Xs)
         return self.fit_predict_sample_resident(sigma, l, noise_var, jitter, want_sd, want_factor)
 
-    def fit_predict(self, X, y, Xs, sigma, l, noise_var, want_sd=True):
-        self.set_train(X, y)
+    def fit_predict(self, X, y, Xs, sigma, l, noise_var, want_sd=True, *, lengthscales=KEEP):
+        self._set_train_ard(X, y, lengthscales)
         self.set_test(Xs)
         return self.fit_predict_resident(sigma, l, noise_var, want_sd)
 
@@ -286,6 +324,15 @@ class GPContext:
         check(self._lib.gpmi_lml_grad(self._h, C.byref(dl), C.byref(ds)))
         return dl.value, ds.value
 
+    def lml_grad_ard(self):
+        """(d_r (d,), dLML/dl, dLML/dsigma, dLML/dnoise_var) at the resident factorisation: the derivatives w.r.t. the
+        relative lengthscales of set_lengthscales (all 1 when none are set), the common lengthscale, the output scale
+        and the noise variance, from one fused pass over K_y^-1 (gpmi_lml_grad_ard)."""
+        d_r = np.empty(self.d)
+        dl, ds, dn = C.c_double(), C.c_double(), C.c_double()
+        check(self._lib.gpmi_lml_grad_ard(self._h, ptr(d_r), C.byref(dl), C.byref(ds), C.byref(dn)))
+        return d_r, dl.value, ds.value, dn.value
+
     def grad_trace(self, a, b, sigma, l, alpha, K_y_inv):
         """The same two traces from gradient_ascent's arguments (tune_hyperparms_regression.py:31)."""
         a = as_f64(a, 2, "a")
@@ -303,14 +350,14 @@ class GPContext:
         return dl.value, ds.value
 
     # ---- binary classification (Laplace approximation) --------------------------------
-    def laplace_fit(self, X, y, sigma, l, *, tol=1e-10, max_iter=100):
+    def laplace_fit(self, X, y, sigma, l, *, tol=1e-10, max_iter=100, lengthscales=KEEP):
         """GPML Algorithm 3.1 (logistic likelihood) on the GPU for labels y in {-1, +1} and the squared-exponential
         kernel sigma**2 exp(-.5 sqdist / l**2).  Returns (log_q, f_hat, iters, converged): the Laplace approximation of
         the log marginal likelihood (GPML eq. 3.32), the posterior mode, the Newton steps taken and whether
         |Psi - Psi_prev| <= tol max(1, |Psi|) was reached (a RuntimeWarning when not).  The mode and the factor of
         B = I + W^1/2 K W^1/2 stay on the device for laplace_predict."""
         import warnings
-        self.set_train(X, y)
+        self._set_train_ard(X, y, lengthscales)
         log_q = C.c_double()
         iters, conv = C.c_int(), C.c_int()
         f_hat = np.empty(self.N)
@@ -331,7 +378,7 @@ class GPContext:
         return f_mean, f_var, prob
 
     # ---- multi-class classification (softmax Laplace approximation) ---------------------
-    def softmax_fit(self, X, labels, n_classes, sigma, l, *, tol=1e-10, max_iter=100):
+    def softmax_fit(self, X, labels, n_classes, sigma, l, *, tol=1e-10, max_iter=100, lengthscales=KEEP):
         """GPML Algorithm 3.3 (softmax likelihood) on the GPU for integer labels in [0, n_classes) and one
         squared-exponential prior sigma**2 exp(-.5 sqdist / l**2) shared by the n_classes latent functions.  Returns
         (log_q, F_hat, iters, converged): the Laplace approximation of the log marginal likelihood, the posterior mode
@@ -340,7 +387,7 @@ class GPContext:
         softmax_predict."""
         import warnings
         lab, n_classes = softmax_labels(labels, n_classes)
-        self.set_train(X, lab)
+        self._set_train_ard(X, lab, lengthscales)
         log_q = C.c_double()
         iters, conv = C.c_int(), C.c_int()
         f_hat = np.empty((n_classes, self.N))

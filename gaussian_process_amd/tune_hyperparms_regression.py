@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .gp import default_context
+from .gp import default_context, split_lengthscale
 
 NOISE_VAR = 0.0005      # tune_hyperparms_regression.py:302
 BO_NOISE_VAR = 0.0001   # tune_hyperparms_regression.py:75
@@ -17,15 +17,23 @@ BO_NOISE_VAR = 0.0001   # tune_hyperparms_regression.py:75
 def compute_mar_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None, n_gpus=None,
                            dist=None):
     """Log marginal likelihood, reference tune_hyperparms_regression.py:292-313.
-    X_test is accepted and unused, exactly as in the reference.  n_gpus / dist: factorise with the covariance
+    X_test is accepted and unused, exactly as in the reference.  l may be a d-vector (one lengthscale per input
+    dimension); a scalar or 1-element l is isotropic and clears any the context carried.  n_gpus / dist: factorise with the covariance
     row-block partitioned over the ranks of the node (every rank makes the same call)."""
     from .GP_regression import _dist_of
+    l, r = split_lengthscale(l)          # a d-vector: one lengthscale per input dimension, common l = 1
     gp = _dist_of(n_gpus, dist)
     if gp is not None:
+        if r is not None:
+            raise ValueError("per-dimension lengthscales (a vector l) are not available on the partitioned path (n_gpus / dist)")
         from ._lib import scalar
         return np.float64(gp.fit(X_train, y_train, scalar(sigma, "sigma"), scalar(l, "l"), noise_var))
     ctx = ctx or default_context()
-    return np.float64(ctx.fit(X_train, y_train, sigma, l, noise_var))
+    try:
+        return np.float64(ctx.fit(X_train, y_train, sigma, l, noise_var, lengthscales=r))
+    finally:
+        if r is not None:
+            ctx.set_lengthscales(None)   # the lengthscales of this call do not outlive it
 
 
 def compute_mar_likelihood_batch(X_train, y_train, triples, *, ctx=None):
@@ -261,3 +269,88 @@ def tune_hyperparms_gradient(X_train, X_test, y_train, num_fun, *, ctx=None, ver
     _, _, _, optimal_likelihood = tune_hyperparms_first(X_train, X_test, y_train, num_fun, sigma, l,
                                                         ctx=ctx, verbose=verbose)   # :410
     return optimal_likelihood
+
+
+# ---------------------------------------------------------------------------------------
+# Per-dimension lengthscales (ARD): the LML with its full gradient -- d lengthscales, the output scale and the noise
+# variance -- from one factorisation and one fused pass over K_y^-1 (gpmi_lml_grad_ard), and a deliberately small tuner
+# on top of it.  The reference has neither; anyone with an optimiser of their own calls lml_and_gradient_ard.
+# ---------------------------------------------------------------------------------------
+ARD_MAX_HALVINGS = 20
+ARD_MAX_LOG_STEP = 1.0   # no parameter moves by more than a factor e in one trial step
+
+
+def _ard_lml(ctx, lengthscales, sigma, noise_var):
+    """LML at (lengthscales, sigma, noise_var) for the training set resident in ctx; -inf where K + sI is not PD."""
+    ctx.set_lengthscales(lengthscales)
+    try:
+        return float(ctx.factorize(sigma, 1.0, noise_var))
+    except np.linalg.LinAlgError:
+        return -np.inf
+
+
+def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOISE_VAR, ctx=None):
+    """(lml, d_lengthscales (d,), d_sigma, d_noise): the log marginal likelihood of the squared-exponential kernel with one
+    absolute lengthscale per input dimension, and its derivatives w.r.t. those lengthscales, sigma and noise_var.  The
+    context keeps the lengthscales and the factorisation (alpha, predict and lml_grad_ard work on it afterwards)."""
+    ctx = ctx or default_context()
+    ls = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
+    lml = ctx.fit(X_train, y_train, sigma, 1.0, noise_var, lengthscales=ls)
+    d_r, _, d_sigma, d_noise = ctx.lml_grad_ard()      # common l = 1: d_r is the derivative w.r.t. the lengthscales
+    return np.float64(lml), d_r, d_sigma, d_noise
+
+
+def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise_var=NOISE_VAR, max_iter=100, tol=1e-6,
+                        ctx=None):
+    """Maximise the log marginal likelihood over (lengthscales, sigma, noise_var) by gradient ascent on their logarithms.
+
+    Every iteration takes the gradient at the current point (d LML / d log p = p * d LML / d p) and tries a step along
+    it; a step that lowers the LML (or leaves K + sI not positive definite) is halved, at most ARD_MAX_HALVINGS times,
+    before being accepted -- the accept / halve rule of the classifiers' Newton loops.  The step length carries over,
+    doubled, to the next iteration, and never moves a parameter by more than a factor e.  Stops after max_iter
+    iterations or when |dLML| <= tol * max(1, |LML|).
+
+    :param lengthscales: initial per-dimension lengthscales (default: all 1)
+    :return: (lengthscales (d,), sigma, noise_var, lml, trace): the parameters reached, their LML and the LML of every
+             accepted point, the initial one first.  The context is left with those lengthscales and their factor.
+    """
+    ctx = ctx or default_context()
+    X_train = np.asarray(X_train, dtype=np.float64)
+    d = X_train.shape[1]
+    ls = np.ones(d) if lengthscales is None else np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy()
+    if ls.shape[0] != d or not np.all(np.isfinite(ls)) or np.any(ls <= 0):
+        raise ValueError("lengthscales must be %d finite positive numbers" % d)
+    if not (sigma > 0 and noise_var > 0):
+        raise ValueError("sigma and noise_var must be positive (the ascent runs on their logarithms)")
+    ctx.set_train(X_train, y_train)
+    theta = np.log(np.concatenate([ls, [float(sigma), float(noise_var)]]))
+    lml = _ard_lml(ctx, np.exp(theta[:d]), np.exp(theta[d]), np.exp(theta[d + 1]))
+    if not np.isfinite(lml):
+        raise np.linalg.LinAlgError("Matrix is not positive definite")
+    trace = [lml]
+    step = None
+    for _ in range(int(max_iter)):
+        d_r, _, d_sigma, d_noise = ctx.lml_grad_ard()
+        g = np.concatenate([d_r, [d_sigma, d_noise]]) * np.exp(theta)
+        gmax = float(np.max(np.abs(g)))
+        if not np.isfinite(gmax) or gmax == 0.0:
+            break
+        cap = ARD_MAX_LOG_STEP / gmax
+        step = cap if step is None else min(step, cap)
+        for halving in range(ARD_MAX_HALVINGS + 1):
+            trial = theta + step * g
+            lml_new = _ard_lml(ctx, np.exp(trial[:d]), np.exp(trial[d]), np.exp(trial[d + 1]))
+            if lml_new >= lml or halving == ARD_MAX_HALVINGS:
+                break
+            step *= 0.5
+        if not np.isfinite(lml_new):         # twenty halvings and still no factor: stay where the last one was
+            _ard_lml(ctx, np.exp(theta[:d]), np.exp(theta[d]), np.exp(theta[d + 1]))
+            break
+        theta = trial
+        delta = abs(lml_new - lml)
+        lml = lml_new
+        trace.append(lml)
+        step *= 2.0
+        if delta <= tol * max(1.0, abs(lml)):
+            break
+    return np.exp(theta[:d]), float(np.exp(theta[d])), float(np.exp(theta[d + 1])), np.float64(lml), np.asarray(trace)

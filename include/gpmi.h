@@ -194,8 +194,31 @@ int gpmi_post_sample(gpmi_ctx* ctx, double jitter, const double* Z, int64_t num_
  *   d_sigma = .5 * trace((alpha alpha^T - K_y^-1) @ sigma_grad), sigma_grad = 2 sigma exp(-.5 sqdist/l^2)
  *                                                     tune_hyperparms_regression.py:46-51 (commented out there)
  * with K_y^-1 = inv(L.T) @ inv(L) (:144) formed on the device from the resident L.
- * Squared-exponential kernel only. */
+ * Squared-exponential kernel only.  With lengthscales set (gpmi_set_lengthscales) sqdist is that of the scaled inputs and
+ * d_ell the derivative w.r.t. the common multiplier l. */
 int gpmi_lml_grad(gpmi_ctx* ctx, double* d_ell, double* d_sigma);
+/* Per-dimension lengthscales (automatic relevance determination).  The context carries relative lengthscales r_k > 0,
+ * k < d (default: all 1), and every squared-exponential covariance it builds becomes
+ *   K_ij = sigma^2 exp(-.5 / l^2 * sum_k ((x_ik - x_jk) / r_k)^2)
+ * -- the effective lengthscale of dimension k is l * r_k, with l the argument every call already takes.  The scaling is
+ * done on the inputs: z = x / r, one IEEE division per element on the device, and factorisation, prediction, posterior
+ * samples, gpmi_lml_batch, both Laplace classifiers and the gradients read z.  gpmi_rbf / gpmi_cov take their inputs as
+ * arguments and are not affected.
+ *   r == NULL or d == 0: back to the isotropic state (the context then reads the buffers it always read).
+ *   otherwise every r_k must be finite and > 0 and d must equal the resident training set's d (GPMI_ERR_BAD_ARG).
+ * May be called before or after gpmi_set_train / gpmi_set_test and repeatedly: the raw inputs stay on the device and the
+ * scaled copies are regenerated there (d doubles go up).  Drops any resident regression factor, binary Laplace fit and
+ * softmax fit, as a new gpmi_set_train does.  A later gpmi_set_train with another d clears the lengthscales; one with the
+ * same d keeps them.  Squared-exponential kernel (kind 0) only: a fit with another kind is refused while they are set. */
+int gpmi_set_lengthscales(gpmi_ctx* ctx, const double* r, int64_t d);
+/* The gradient of the log marginal likelihood w.r.t. every hyper-parameter at the resident factorisation, with
+ * W = alpha alpha^T - K_y^-1 and z = x / r (z = x when no lengthscales are set):
+ *   d_r[k]  = .5 * sum_ij W_ij K_ij (z_ik - z_jk)^2 / (l^2 r_k)     (d doubles; d LML / d r_k)
+ *   d_ell, d_sigma as gpmi_lml_grad (to rounding: another kernel adds them up)
+ *   d_noise = .5 * (alpha^T alpha - trace(K_y^-1))                   (d LML / d noise_var)
+ * Any output may be NULL.  sum_k r_k d_r[k] == l * d_ell (K depends on l * r_k only).  Refuses what gpmi_lml_grad
+ * refuses.  One fused pass over K_y^-1 per 32 dimensions; the sums are bitwise reproducible from run to run. */
+int gpmi_lml_grad_ard(gpmi_ctx* ctx, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
 /* The same two traces from the arguments gradient_ascent(a, b, sigma, l, alpha, K_y) receives
  * (tune_hyperparms_regression.py:31): a, b: N x d; alpha: N; K_y_inv: N x N row-major (host).
  * One fused N^2 pass instead of the reference's two N x N products (:55). */
