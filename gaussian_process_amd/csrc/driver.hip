@@ -311,7 +311,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (with_test) c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
     c->sig2 = sigma * sigma;
     c->coef = -.5 * (1 / (ell * ell));      // GP_regression.py:19 evaluation order
-    c->sigma = sigma; c->ell = ell;
+    c->sigma = sigma; c->ell = ell; c->noise = noise_var;
     double* A = c->A.as<double>();
     const int64_t big = std::numeric_limits<int64_t>::max();
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, s));

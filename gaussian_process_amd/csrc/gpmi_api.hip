@@ -76,7 +76,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out})
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -567,6 +567,48 @@ int gpmi_predict(gpmi_ctx* c, const double* Xs, int64_t n, double* mu, double* o
     return gpmi_predict_resident(c, mu, out2, want_sd);
 }
 
+// The front of both LML gradients and of the leave-one-out calls, inside a timer span of the caller's slot that it opens:
+// alpha = L^-T m (a5; the caller reads the backward solve's give-up word), U = L^-T by the TRSM sweep on the identity
+// and -- want_kn -- Kn = -U U^T on the lower tiles (row block i needs the columns from its first row on only).
+static int grad_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span) {
+    hipStream_t s = c->stream;
+    const int64_t Np = c->Np, ld = c->ldA;
+    HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
+    if (want_kn) HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
+    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
+    *span = c->span_begin(slot);
+    // alpha = L^-T m (a5)
+    double* alpha = c->vec.as<double>();
+    HIP_TRY(hipMemcpyAsync(alpha, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
+    if (c->factor_fused) {
+        HIP_TRY(backward_solve_fused(c, alpha, alpha + Np));
+        alpha += Np;
+    } else {
+        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), ld, alpha, Np));
+    }
+    *alpha_out = alpha;
+    // U = I * L^-T
+    double* U = c->U.as<double>();
+    HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
+    HIP_TRY(launch_set_identity_diag(s, U, ld, Np));
+    HIP_TRY(solve_sweep(c, U, ld, Np, true));
+    if (!want_kn) return GPMI_OK;
+    // Kn = -U U^T, lower tiles: row block i needs columns >= its first row only
+    double* Kn = c->Kn.as<double>();
+    HIP_TRY(launch_fill_rows(s, Kn, ld, Np, Np, 0.0));
+    const int64_t NB = c->block(Np);
+    for (int64_t r0 = 0; r0 < Np; r0 += NB) {
+        const int64_t nb = std::min<int64_t>(NB, Np - r0);
+        GemmArgs g;
+        g.C = Kn + r0 * ld; g.A = U + r0 * ld + r0; g.B = U + r0;
+        g.ldc = g.lda = g.ldb = ld;
+        g.M = nb; g.N = r0 + nb; g.K = Np - r0;
+        g.mode = 0; g.lower = 1; g.diag_off = r0;
+        HIP_TRY(launch_gemm_nt(s, g));
+    }
+    return GPMI_OK;
+}
+
 // f2 -- gradient of the log marginal likelihood at the resident factorisation:
 // 0.5 * tr((alpha alpha^T - K_y^-1) dK/dtheta)  (tune_hyperparms_regression.py:43-57; the reference
 // builds K_y^-1 = inv(L.T) inv(L) at :144 and two N x N products).  Here: U = L^-T by the TRSM
@@ -581,39 +623,13 @@ int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     tn.panel_fused = c->factor_fused;
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
-    const int64_t Np = c->Np, ld = c->ldA;
+    const int64_t ld = c->ldA;
     c->timers_reset({GPMI_T_GRAD});
-    HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
-    HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
-    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
-    size_t sp = c->span_begin(GPMI_T_GRAD);
-    // alpha = L^-T m (a5)
-    double* alpha = c->vec.as<double>();
-    HIP_TRY(hipMemcpyAsync(alpha, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
-    if (c->factor_fused) {
-        HIP_TRY(backward_solve_fused(c, alpha, alpha + Np));
-        alpha += Np;
-    } else {
-        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), ld, alpha, Np));
-    }
-    // U = I * L^-T
-    double* U = c->U.as<double>();
-    HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
-    HIP_TRY(launch_set_identity_diag(s, U, ld, Np));
-    HIP_TRY(solve_sweep(c, U, ld, Np, true));
-    // Kn = -U U^T, lower tiles: row block i needs columns >= its first row only
+    double* alpha = nullptr;
+    size_t sp = 0;
+    int rc = grad_front(c, GPMI_T_GRAD, true, &alpha, &sp);
+    if (rc) return rc;
     double* Kn = c->Kn.as<double>();
-    HIP_TRY(launch_fill_rows(s, Kn, ld, Np, Np, 0.0));
-    const int64_t NB = c->block(Np);
-    for (int64_t r0 = 0; r0 < Np; r0 += NB) {
-        const int64_t nb = std::min<int64_t>(NB, Np - r0);
-        GemmArgs g;
-        g.C = Kn + r0 * ld; g.A = U + r0 * ld + r0; g.B = U + r0;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = nb; g.N = r0 + nb; g.K = Np - r0;
-        g.mode = 0; g.lower = 1; g.diag_off = r0;
-        HIP_TRY(launch_gemm_nt(s, g));
-    }
     GradArgs a;
     a.A = a.B = c->x_train(); a.nA = a.nB = c->N; a.d = c->d;
     a.row0 = 0; a.nrows = c->N;
@@ -654,36 +670,13 @@ int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     tn.panel_fused = c->factor_fused;
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
-    const int64_t Np = c->Np, ld = c->ldA;
+    const int64_t ld = c->ldA;
     c->timers_reset({GPMI_T_GRAD});
-    HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
-    HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
-    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
-    size_t sp = c->span_begin(GPMI_T_GRAD);
-    double* alpha = c->vec.as<double>();
-    HIP_TRY(hipMemcpyAsync(alpha, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
-    if (c->factor_fused) {
-        HIP_TRY(backward_solve_fused(c, alpha, alpha + Np));
-        alpha += Np;
-    } else {
-        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), ld, alpha, Np));
-    }
-    double* U = c->U.as<double>();
-    HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
-    HIP_TRY(launch_set_identity_diag(s, U, ld, Np));
-    HIP_TRY(solve_sweep(c, U, ld, Np, true));
+    double* alpha = nullptr;
+    size_t sp = 0;
+    int rc = grad_front(c, GPMI_T_GRAD, true, &alpha, &sp);
+    if (rc) return rc;
     double* Kn = c->Kn.as<double>();
-    HIP_TRY(launch_fill_rows(s, Kn, ld, Np, Np, 0.0));
-    const int64_t NB = c->block(Np);
-    for (int64_t r0 = 0; r0 < Np; r0 += NB) {
-        const int64_t nb = std::min<int64_t>(NB, Np - r0);
-        GemmArgs g;
-        g.C = Kn + r0 * ld; g.A = U + r0 * ld + r0; g.B = U + r0;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = nb; g.N = r0 + nb; g.K = Np - r0;
-        g.mode = 0; g.lower = 1; g.diag_off = r0;
-        HIP_TRY(launch_gemm_nt(s, g));
-    }
     GradArdArgs a;
     a.Z = c->x_train(); a.n = c->N; a.d = c->d;
     a.alpha = alpha; a.Kn = Kn; a.ld = ld; a.coef = c->coef;
@@ -712,6 +705,108 @@ int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
     if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
     if (d_noise) *d_noise = .5 * sums[(size_t)w + 2];
+    return GPMI_OK;
+}
+
+// Leave-one-out cross-validation at the resident factorisation (GPML section 5.4.2, eqs. 5.10-5.12): with alpha =
+// K_y^-1 y and kappa_i = [K_y^-1]_ii the prediction of y_i from the other N - 1 points is N(y_i - alpha_i / kappa_i,
+// 1 / kappa_i).  alpha and U = L^-T as in gpmi_lml_grad; kappa_i is the squared norm of row i of U (K_y^-1 = U U^T), so
+// the N^3/3 product -U U^T of the gradients is not needed.  Reads L, m and y only: every kernel kind.
+int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
+    if (!c) return fail_arg("gpmi_loo: null context");
+    if (!c->have_factor) return fail_arg("gpmi_loo: no regression factorisation resident (call gpmi_factorize)");
+    HIP_TRY(hipSetDevice(c->device));
+    Tuning tn = c->tune;
+    tn.panel_fused = c->factor_fused;
+    TuneScope tune_scope(&tn);
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, Np = c->Np, ld = c->ldA;
+    c->timers_reset({GPMI_T_LOO});
+    HIP_TRY(c->loov.ensure((size_t)(4 * Np + 8) * 8));
+    double* kappa = c->loov.as<double>();
+    double *dmu = kappa + Np, *dvar = dmu + Np, *dlogp = dvar + Np, *dsum = dlogp + Np;
+    double* alpha = nullptr;
+    size_t sp = 0;
+    int rc = grad_front(c, GPMI_T_LOO, false, &alpha, &sp);
+    if (rc) return rc;
+    HIP_TRY(launch_loo_kappa(s, c->U.as<double>(), ld, N, kappa));
+    HIP_TRY(launch_loo_points(s, c->y.as<double>(), alpha, kappa, N, dmu, dvar, dlogp, dsum));
+    c->span_end(sp);
+    if (mu) HIP_TRY(hipMemcpyAsync(mu, dmu, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    if (var) HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    if (logp) HIP_TRY(hipMemcpyAsync(logp, dlogp, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    double sum = 0.0;
+    HIP_TRY(hipMemcpyAsync(&sum, dsum, 8, hipMemcpyDeviceToHost, s));
+    int gave_up = 0;      // the one-launch backward solve's "a poll gave up" word, as gpmi_get_alpha reads it
+    if (c->factor_fused && tuning().trsv_vinv >= 2)
+        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c->timers_collect();
+    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_loo: the single-launch backward solve gave up waiting for a block");
+    if (loo) *loo = sum;
+    return GPMI_OK;
+}
+
+// The derivatives of the leave-one-out log probability (GPML eq. 5.13) w.r.t. l, sigma and the noise variance:
+//   sum_i (alpha_i r_i - .5 (1 + alpha_i^2 / kappa_i) s_i) / kappa_i,   r = Z alpha,  s_i = [Z K_y^-1]_ii,  Z = K_y^-1 dK_y
+// alpha, U and Kn = -K_y^-1 as in gpmi_lml_grad; kappa from U as in gpmi_loo; Kn mirrored into a full matrix; D = K o sq
+// (dK/dl = D / l^3) built in full into U's buffer, which is dead by then; one pass over the rows of D for t = D alpha and
+// one over the rows of Kn for c_i = sum_a Kn_ia^2, Kn alpha and Kn t; then K_y^-1 D one row block at a time (the routed
+// GEMM into an NB x ld workspace, 2 N^3 flops in all) with s_i read off each block by a row dot with Kn -- the product is
+// never stored whole.  sigma and the noise need no N^3 product (dK_y = 2 (K_y - noise I) / sigma and I).
+int gpmi_loo_grad(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) {
+    if (!c) return fail_arg("gpmi_loo_grad: null context");
+    if (!c->have_factor) return fail_arg("gpmi_loo_grad: no regression factorisation resident (call gpmi_factorize)");
+    if (c->kind != 0) return fail_arg("gpmi_loo_grad: squared-exponential kernel only");
+    HIP_TRY(hipSetDevice(c->device));
+    Tuning tn = c->tune;
+    tn.panel_fused = c->factor_fused;
+    TuneScope tune_scope(&tn);
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, Np = c->Np, ld = c->ldA;
+    const int64_t NB = std::min<int64_t>(c->block(Np), Np);
+    c->timers_reset({GPMI_T_LOO});
+    HIP_TRY(c->loov.ensure((size_t)(6 * Np + 8) * 8));
+    HIP_TRY(c->loow.ensure((size_t)NB * ld * 8));
+    double* kappa = c->loov.as<double>();
+    double *cn = kappa + Np, *qn = cn + Np, *un = qn + Np, *t = un + Np, *sn = t + Np, *sums = sn + Np;
+    double* alpha = nullptr;
+    size_t sp = 0;
+    int rc = grad_front(c, GPMI_T_LOO, true, &alpha, &sp);
+    if (rc) return rc;
+    double *D = c->U.as<double>(), *Kn = c->Kn.as<double>(), *W = c->loow.as<double>();
+    HIP_TRY(launch_loo_kappa(s, D, ld, N, kappa));               // U is still L^-T here
+    HIP_TRY(launch_mirror_lower(s, Kn, ld, Np));
+    HIP_TRY(launch_loo_dmat(s, c->x_train(), N, c->d, c->coef, c->sig2, D, ld, Np));
+    HIP_TRY(launch_row_pass(s, D, ld, N, alpha, nullptr, nullptr, t, nullptr));
+    HIP_TRY(launch_row_pass(s, Kn, ld, N, alpha, t, cn, qn, un));
+    for (int64_t r0 = 0; r0 < N; r0 += NB) {                     // a row block of padding only has nothing to give
+        const int64_t nb = std::min<int64_t>(NB, Np - r0);
+        HIP_TRY(launch_fill_rows(s, W, ld, nb, Np, 0.0));
+        GemmArgs g;                                              // W = -Kn[r0 .. r0 + nb) D^T = (K_y^-1 D) rows; D is symmetric
+        g.C = W; g.A = Kn + r0 * ld; g.B = D;
+        g.ldc = g.lda = g.ldb = ld;
+        g.M = nb; g.N = Np; g.K = Np;
+        g.mode = 0; g.lower = 0; g.diag_off = 0;
+        HIP_TRY(launch_gemm_nt(s, g));
+        HIP_TRY(launch_row_dot2(s, W, ld, Kn + r0 * ld, ld, std::min<int64_t>(nb, N - r0), N, sn + r0));
+    }
+    LooGradArgs a;
+    a.alpha = alpha; a.kappa = kappa; a.cn = cn; a.qn = qn; a.un = un; a.sn = sn;
+    a.n = N; a.noise = c->noise; a.out3 = sums;
+    HIP_TRY(launch_loo_grad_sums(s, a));
+    c->span_end(sp);
+    double h[3] = {0.0, 0.0, 0.0};
+    HIP_TRY(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, s));
+    int gave_up = 0;
+    if (c->factor_fused && tuning().trsv_vinv >= 2)
+        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    c->timers_collect();
+    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_loo_grad: the single-launch backward solve gave up waiting for a block");
+    if (d_ell) *d_ell = h[0] / (c->ell * c->ell * c->ell);
+    if (d_sigma) *d_sigma = 2.0 / c->sigma * h[1];
+    if (d_noise) *d_noise = h[2];
     return GPMI_OK;
 }
 

@@ -175,6 +175,8 @@ struct gpmi_ctx {
     DevBuf U, Kn, gpart;     // f2: L^-T, -(K+sI)^-1, per-tile partial sums of the gradient trace
     DevBuf gsum;             // gpmi_lml_grad_ard: the d + 3 sums, reduced on the device
     double sigma = 1.0, ell = 1.0;   // hyper-parameters of the resident factorisation
+    double noise = 0.0;              // ... and its noise variance (regression factorisations only)
+    DevBuf loov, loow;       // gpmi_loo / gpmi_loo_grad: the per-point vectors; the NB x ld row block of K_y^-1 D
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
     // A Laplace factor is not a regression factor: gpmi_laplace_fit clears have_factor, every regression factorisation

@@ -183,6 +183,37 @@ hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a);
 // Z[i][k] = X[i][k] / r[k]: one IEEE division per element
 hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z);
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n);
+// ---- leave-one-out cross-validation (GPML 5.4.2), grad.hip ----
+// Every kernel reads rows and columns < n only (the identity padding contributes nothing), reads matrices with 16-byte
+// loads (ld even, base 16-byte aligned, n < the padded size when n is odd) and adds in a fixed order.
+// kappa[i] = sum_{i <= j < n} U[i][j]^2, the diagonal of K_y^-1 = U U^T from the upper triangular U = L^-T
+hipError_t launch_loo_kappa(hipStream_t s, const double* U, int64_t ld, int64_t n, double* kappa);
+// mu = y - alpha / kappa, var = 1 / kappa, logp = -.5 log var - (y - mu)^2 / (2 var) - .5 log 2 pi (n doubles each), and
+// *sum = sum_i logp[i]
+hipError_t launch_loo_points(hipStream_t s, const double* y, const double* alpha, const double* kappa, int64_t n,
+                             double* mu, double* var, double* logp, double* sum);
+// upper(i < j) <- lower(j, i) over the np x np matrix (np a multiple of 64)
+hipError_t launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np);
+// D[a][b] = sig2 exp(coef sq_ab) sq_ab for a, b < n and 0 on the padding, np x np in full (np a multiple of 128)
+hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, double* D,
+                           int64_t ld, int64_t np);
+// per row i < n of M: sq[i] = sum_j M_ij^2 (sq may be null), d0[i] = sum_j M_ij x0[j], d1[i] = sum_j M_ij x1[j] (x1, d1
+// may be null); x0, x1 hold at least n + 1 doubles
+hipError_t launch_row_pass(hipStream_t s, const double* M, int64_t ld, int64_t n, const double* x0, const double* x1,
+                           double* sq, double* d0, double* d1);
+// out[i] = sum_{j < n} C[i][j] * B[i][j] for i < nrows
+hipError_t launch_row_dot2(hipStream_t s, const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t nrows,
+                           int64_t n, double* out);
+// GPML eq. 5.13 without its per-parameter factors.  With Kn = -K_y^-1: cn = row sums of Kn^2, qn = Kn alpha,
+// un = Kn (D alpha), sn[i] = -[K_y^-1 D K_y^-1]_ii.  out3[0] (l): r = -un, s = -sn; out3[1] (sigma): r = alpha + noise qn,
+// s = kappa - noise cn; out3[2] (noise): r = -qn, s = cn; each sum_i (alpha_i r_i - .5 (1 + alpha_i^2 / kappa_i) s_i) / kappa_i
+struct LooGradArgs {
+    const double *alpha, *kappa, *cn, *qn, *un, *sn;
+    int64_t n;
+    double noise;
+    double* out3;
+};
+hipError_t launch_loo_grad_sums(hipStream_t s, const LooGradArgs& a);
 
 // ---- solve.hip -------------------------------------------------------------
 // dot[i] = sum_j V[i][j]*m[j], sq[i] = sum_j V[i][j]^2, j < ncols (fixed order)

@@ -15,6 +15,7 @@
 // fixed order (bitwise reproducible); the host adds the per-tile partials in order.
 #include <algorithm>
 
+#include "exp_dev.h"
 #include "gpmi_internal.h"
 
 namespace gpmi {
@@ -281,6 +282,217 @@ __global__ void set_identity_kernel(double* V, int64_t ld, int64_t n) {
     if (i < n) V[i * ld + i] = 1.0;
 }
 
+// ---- leave-one-out cross-validation (GPML section 5.4.2) ------------------------------------------------------------
+// Small N^2 passes around the N^3 products of gpmi_loo / gpmi_loo_grad (gpmi_api.hip).  The row kernels give one wave a
+// row: lane t reads the column pairs 2t, 2t + 128, ... with 16-byte loads (a wave reads 1 KiB per instruction) and adds
+// them in that order, the 64 lanes meet in a butterfly -- the same order every run.  They read rows and columns < n
+// only: whatever the identity padding holds contributes nothing.
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// kappa_i = sum_{j >= i} U_ij^2: the diagonal of K_y^-1 = U U^T, U = L^-T upper triangular
+__global__ __launch_bounds__(256) void loo_kappa_kernel(const double* __restrict__ U, int64_t ld, int64_t n,
+                                                        double* __restrict__ kappa) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;                                          // wave-uniform
+    const double* row = U + i * ld;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t j = (i & ~(int64_t)1) + 2 * lane; j < n; j += 128) {
+        const dbl2 v = *reinterpret_cast<const dbl2*>(row + j);
+        const double a = (j >= i) ? v.x : 0.0, b = (j + 1 < n) ? v.y : 0.0;
+        acc = fma(a, a, acc);
+        acc = fma(b, b, acc);
+    }
+    acc = wave_sum64(acc);
+    if (lane == 0) kappa[i] = acc;
+}
+
+__global__ __launch_bounds__(256) void loo_points_kernel(const double* __restrict__ y, const double* __restrict__ alpha,
+                                                         const double* __restrict__ kappa, int64_t n, double* __restrict__ mu,
+                                                         double* __restrict__ var, double* __restrict__ logp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double k = kappa[i], yi = y[i];
+    const double v = 1.0 / k, m = yi - alpha[i] / k, e = yi - m;
+    mu[i] = m;
+    var[i] = v;
+    logp[i] = -.5 * log(v) - e * e / (2.0 * v) - 0.91893853320467274178;      // .5 log(2 pi)
+}
+
+// upper(i < j) <- lower(j, i), 64 x 64 tiles transposed through LDS (rows padded by one double: a wave's column read
+// touches every bank pair once per 32 lanes)
+__global__ __launch_bounds__(256) void mirror_lower_kernel(double* A, int64_t ld) {
+    __shared__ double tile[64][65];
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj > ti) return;
+    const int c = threadIdx.x & 63, r0 = threadIdx.x >> 6;
+    const double* src = A + ((int64_t)ti * 64) * ld + (int64_t)tj * 64;
+    for (int r = r0; r < 64; r += 4) tile[r][c] = src[(int64_t)r * ld + c];
+    __syncthreads();
+    double* dst = A + ((int64_t)tj * 64) * ld + (int64_t)ti * 64;
+    for (int r = r0; r < 64; r += 4)
+        if (ti != tj || c > r) dst[(int64_t)r * ld + c] = tile[c][r];
+}
+
+// D_ab = K_ab sq_ab = sig2 exp(coef sq_ab) sq_ab in full (dK/dl = D / l^3), zero on padded rows and columns.  The tile
+// loop, the staging and the squared distance of grad_trace_kernel; exp by the K build's polynomial while every lane of
+// the wave is inside its domain.  D_ab and D_ba are the same bits ((a - b)^2 == (b - a)^2, the same order over k).
+struct DmatDev {
+    const double* Z;
+    int64_t n;
+    int d;
+    double coef, sig2;
+    double* D;
+    int64_t ld;
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void loo_dmat_kernel(const DmatDev p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    const int d = p.d;
+    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
+    const int tid = threadIdx.x;
+    double* As = lds;               // [RT][d]
+    double* Bs = lds + RT * d;      // [d][RT]
+    if (LDS) {
+        for (int e = tid; e < RT * d; e += 256) {
+            const int r = e / d, k = e - r * d;
+            const int64_t ga = grow0 + r, gb = gcol0 + r;
+            As[r * d + k] = (ga < p.n) ? p.Z[ga * d + k] : 0.0;
+            Bs[k * RT + r] = (gb < p.n) ? p.Z[gb * d + k] : 0.0;
+        }
+        __syncthreads();
+    }
+    const int cp = tid & 63, rg = tid >> 6;
+    const int64_t gc = gcol0 + 2 * cp;
+    const bool in0 = gc < p.n, in1 = gc + 1 < p.n;
+    for (int r = 0; r < 32; ++r) {
+        const int lr = 32 * rg + r;
+        const int64_t gr = grow0 + lr;
+        const bool inr = gr < p.n;                               // wave-uniform
+        double s0 = 0.0, s1 = 0.0;
+        if (LDS) {
+            const double* ar = &As[lr * d];
+            const double* bc = &Bs[2 * cp];
+            for (int k = 0; k < d; ++k) {
+                const double a = ar[k];
+                const double e0 = a - bc[k * RT], e1 = a - bc[k * RT + 1];
+                s0 = fma(e0, e0, s0);
+                s1 = fma(e1, e1, s1);
+            }
+        } else {
+            const double* ar = p.Z + (inr ? gr : 0) * d;
+            const double* b0 = p.Z + (in0 ? gc : 0) * d;
+            const double* b1 = p.Z + (in1 ? gc + 1 : 0) * d;
+            for (int k = 0; k < d; ++k) {
+                const double a = ar[k];
+                const double e0 = a - b0[k], e1 = a - b1[k];
+                s0 = fma(e0, e0, s0);
+                s1 = fma(e1, e1, s1);
+            }
+        }
+        const double x0 = p.coef * s0, x1 = p.coef * s1;
+        double e0, e1;
+        const bool ok = (x0 >= -700.0) & (x0 <= 0.0) & (x1 >= -700.0) & (x1 <= 0.0);
+        if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
+            e0 = exp_neg_fast(x0);
+            e1 = exp_neg_fast(x1);
+        } else {
+            e0 = exp(x0);
+            e1 = exp(x1);
+        }
+        dbl2 v;
+        v.x = (inr && in0) ? (p.sig2 * e0) * s0 : 0.0;
+        v.y = (inr && in1) ? (p.sig2 * e1) * s1 : 0.0;
+        *reinterpret_cast<dbl2*>(p.D + gr * p.ld + gc) = v;
+    }
+}
+
+// per row i < n: sq_i = sum_j M_ij^2, d0_i = sum_j M_ij x0_j, d1_i = sum_j M_ij x1_j (FULL), or d0 alone
+template <bool FULL>
+__global__ __launch_bounds__(256) void row_pass_kernel(const double* __restrict__ M, int64_t ld, int64_t n,
+                                                       const double* __restrict__ x0, const double* __restrict__ x1,
+                                                       double* __restrict__ sq, double* __restrict__ d0, double* __restrict__ d1) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;                                          // wave-uniform
+    const double* row = M + i * ld;
+    double as = 0.0, a0 = 0.0, a1 = 0.0;
+#pragma unroll 4
+    for (int64_t j = 2 * lane; j < n; j += 128) {
+        const bool in1 = j + 1 < n;
+        const dbl2 m = *reinterpret_cast<const dbl2*>(row + j);
+        const dbl2 u = *reinterpret_cast<const dbl2*>(x0 + j);
+        const double my = in1 ? m.y : 0.0;
+        a0 = fma(m.x, u.x, a0);
+        a0 = fma(my, in1 ? u.y : 0.0, a0);
+        if (FULL) {
+            const dbl2 w = *reinterpret_cast<const dbl2*>(x1 + j);
+            as = fma(m.x, m.x, as);
+            as = fma(my, my, as);
+            a1 = fma(m.x, w.x, a1);
+            a1 = fma(my, in1 ? w.y : 0.0, a1);
+        }
+    }
+    a0 = wave_sum64(a0);
+    if (FULL) { as = wave_sum64(as); a1 = wave_sum64(a1); }
+    if (lane == 0) {
+        d0[i] = a0;
+        if (FULL) { sq[i] = as; d1[i] = a1; }
+    }
+}
+
+// out_i = sum_{j < n} C_ij B_ij
+__global__ __launch_bounds__(256) void row_dot2_kernel(const double* __restrict__ C, int64_t ldc, const double* __restrict__ B,
+                                                       int64_t ldb, int64_t nrows, int64_t n, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nrows) return;                                      // wave-uniform
+    const double* c = C + i * ldc;
+    const double* b = B + i * ldb;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int64_t j = 2 * lane; j < n; j += 128) {
+        const dbl2 u = *reinterpret_cast<const dbl2*>(c + j);
+        const dbl2 v = *reinterpret_cast<const dbl2*>(b + j);
+        acc = fma(u.x, v.x, acc);
+        acc = fma((j + 1 < n) ? u.y : 0.0, (j + 1 < n) ? v.y : 0.0, acc);
+    }
+    acc = wave_sum64(acc);
+    if (lane == 0) out[i] = acc;
+}
+
+// block 0: l, block 1: sigma, block 2: noise (gpmi_internal.h: LooGradArgs).  Thread t adds points t, t + 256, ... in
+// order, then a fixed tree.
+__global__ __launch_bounds__(256) void loo_grad_sums_kernel(const LooGradArgs p) {
+    __shared__ double sh[256];
+    const int comp = blockIdx.x;
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < p.n; i += 256) {
+        const double a = p.alpha[i], k = p.kappa[i];
+        double r, s;
+        if (comp == 0) { r = -p.un[i]; s = -p.sn[i]; }
+        else if (comp == 1) { r = a + p.noise * p.qn[i]; s = k - p.noise * p.cn[i]; }
+        else { r = -p.qn[i]; s = p.cn[i]; }
+        acc += (a * r - .5 * (1.0 + a * a / k) * s) / k;
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) p.out3[comp] = sh[0];
+}
+
 }  // namespace
 
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n) {
@@ -353,6 +565,62 @@ hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a) {
     } else {
         hipLaunchKernelGGL(grad_trace_kernel<false>, grid, block, 0, s, p);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_loo_kappa(hipStream_t s, const double* U, int64_t ld, int64_t n, double* kappa) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loo_kappa_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, U, ld, n, kappa);
+    return hipGetLastError();
+}
+
+hipError_t launch_loo_points(hipStream_t s, const double* y, const double* alpha, const double* kappa, int64_t n,
+                             double* mu, double* var, double* logp, double* sum) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loo_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, alpha, kappa, n, mu, var, logp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ard_reduce_kernel, dim3(1), dim3(256), 0, s, logp, n, sum);
+    return hipGetLastError();
+}
+
+hipError_t launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np) {
+    if (np <= 0) return hipSuccess;
+    const unsigned T = (unsigned)(np / 64);
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3(T, T), dim3(256), 0, s, A, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, double* D,
+                           int64_t ld, int64_t np) {
+    if (np <= 0 || d <= 0) return hipSuccess;
+    DmatDev p;
+    p.Z = Z; p.n = n; p.d = (int)d; p.coef = coef; p.sig2 = sig2; p.D = D; p.ld = ld;
+    const unsigned T = (unsigned)(np / RT);
+    if (d <= GRAD_MAXD) hipLaunchKernelGGL(loo_dmat_kernel<true>, dim3(T, T), dim3(256), (size_t)2 * RT * d * sizeof(double), s, p);
+    else hipLaunchKernelGGL(loo_dmat_kernel<false>, dim3(T, T), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_row_pass(hipStream_t s, const double* M, int64_t ld, int64_t n, const double* x0, const double* x1,
+                           double* sq, double* d0, double* d1) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (x1) hipLaunchKernelGGL(row_pass_kernel<true>, grid, block, 0, s, M, ld, n, x0, x1, sq, d0, d1);
+    else hipLaunchKernelGGL(row_pass_kernel<false>, grid, block, 0, s, M, ld, n, x0, x1, sq, d0, d1);
+    return hipGetLastError();
+}
+
+hipError_t launch_row_dot2(hipStream_t s, const double* C, int64_t ldc, const double* B, int64_t ldb, int64_t nrows,
+                           int64_t n, double* out) {
+    if (nrows <= 0 || n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(row_dot2_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s, C, ldc, B, ldb, nrows, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_loo_grad_sums(hipStream_t s, const LooGradArgs& a) {
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loo_grad_sums_kernel, dim3(3), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -333,6 +333,23 @@ class GPContext:
         check(self._lib.gpmi_lml_grad_ard(self._h, ptr(d_r), C.byref(dl), C.byref(ds), C.byref(dn)))
         return d_r, dl.value, ds.value, dn.value
 
+    # ---- leave-one-out cross-validation (GPML 5.4.2) ------------------------------------
+    def loo(self):
+        """(mu (N,), var (N,), logp (N,), loo) at the resident regression factorisation: mean and variance of every
+        training target predicted from the other N - 1 points (noise included), its log predictive probability, and
+        their sum, the leave-one-out criterion of GPML eq. 5.11 (gpmi_loo)."""
+        mu, var, logp = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        total = C.c_double()
+        check(self._lib.gpmi_loo(self._h, ptr(mu), ptr(var), ptr(logp), C.byref(total)))
+        return mu, var, logp, total.value
+
+    def loo_grad(self):
+        """(d/dl, d/dsigma, d/dnoise_var) of the leave-one-out log probability at the resident factorisation (GPML
+        eq. 5.13; squared-exponential kernel, gpmi_loo_grad)."""
+        dl, ds, dn = C.c_double(), C.c_double(), C.c_double()
+        check(self._lib.gpmi_loo_grad(self._h, C.byref(dl), C.byref(ds), C.byref(dn)))
+        return dl.value, ds.value, dn.value
+
     def grad_trace(self, a, b, sigma, l, alpha, K_y_inv):
         """The same two traces from gradient_ascent's arguments (tune_hyperparms_regression.py:31)."""
         a = as_f64(a, 2, "a")

@@ -300,6 +300,42 @@ def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOI
     return np.float64(lml), d_r, d_sigma, d_noise
 
 
+def _log_ascent(value, gradient, theta, max_iter, tol):
+    """The accept / halve / step-carry ascent on the logarithms of positive parameters that tune_hyperparms_ard and
+    tune_hyperparms_loo share.  value(theta) -> the criterion at exp(theta), leaving its factorisation resident (-inf
+    where K + sI is not positive definite); gradient() -> its derivatives w.r.t. exp(theta) at the resident point.
+    -> (theta reached, its value, the values of every accepted point, the initial one first)."""
+    cur = value(theta)
+    if not np.isfinite(cur):
+        raise np.linalg.LinAlgError("Matrix is not positive definite")
+    trace = [cur]
+    step = None
+    for _ in range(int(max_iter)):
+        g = gradient() * np.exp(theta)
+        gmax = float(np.max(np.abs(g)))
+        if not np.isfinite(gmax) or gmax == 0.0:
+            break
+        cap = ARD_MAX_LOG_STEP / gmax
+        step = cap if step is None else min(step, cap)
+        for halving in range(ARD_MAX_HALVINGS + 1):
+            trial = theta + step * g
+            new = value(trial)
+            if new >= cur or halving == ARD_MAX_HALVINGS:
+                break
+            step *= 0.5
+        if not np.isfinite(new):             # twenty halvings and still no factor: stay where the last one was
+            value(theta)
+            break
+        theta = trial
+        delta = abs(new - cur)
+        cur = new
+        trace.append(cur)
+        step *= 2.0
+        if delta <= tol * max(1.0, abs(cur)):
+            break
+    return theta, cur, trace
+
+
 def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise_var=NOISE_VAR, max_iter=100, tol=1e-6,
                         ctx=None):
     """Maximise the log marginal likelihood over (lengthscales, sigma, noise_var) by gradient ascent on their logarithms.
@@ -324,33 +360,70 @@ def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise
         raise ValueError("sigma and noise_var must be positive (the ascent runs on their logarithms)")
     ctx.set_train(X_train, y_train)
     theta = np.log(np.concatenate([ls, [float(sigma), float(noise_var)]]))
-    lml = _ard_lml(ctx, np.exp(theta[:d]), np.exp(theta[d]), np.exp(theta[d + 1]))
-    if not np.isfinite(lml):
-        raise np.linalg.LinAlgError("Matrix is not positive definite")
-    trace = [lml]
-    step = None
-    for _ in range(int(max_iter)):
+
+    def value(th):
+        return _ard_lml(ctx, np.exp(th[:d]), np.exp(th[d]), np.exp(th[d + 1]))
+
+    def gradient():
         d_r, _, d_sigma, d_noise = ctx.lml_grad_ard()
-        g = np.concatenate([d_r, [d_sigma, d_noise]]) * np.exp(theta)
-        gmax = float(np.max(np.abs(g)))
-        if not np.isfinite(gmax) or gmax == 0.0:
-            break
-        cap = ARD_MAX_LOG_STEP / gmax
-        step = cap if step is None else min(step, cap)
-        for halving in range(ARD_MAX_HALVINGS + 1):
-            trial = theta + step * g
-            lml_new = _ard_lml(ctx, np.exp(trial[:d]), np.exp(trial[d]), np.exp(trial[d + 1]))
-            if lml_new >= lml or halving == ARD_MAX_HALVINGS:
-                break
-            step *= 0.5
-        if not np.isfinite(lml_new):         # twenty halvings and still no factor: stay where the last one was
-            _ard_lml(ctx, np.exp(theta[:d]), np.exp(theta[d]), np.exp(theta[d + 1]))
-            break
-        theta = trial
-        delta = abs(lml_new - lml)
-        lml = lml_new
-        trace.append(lml)
-        step *= 2.0
-        if delta <= tol * max(1.0, abs(lml)):
-            break
+        return np.concatenate([d_r, [d_sigma, d_noise]])
+
+    theta, lml, trace = _log_ascent(value, gradient, theta, max_iter, tol)
     return np.exp(theta[:d]), float(np.exp(theta[d])), float(np.exp(theta[d + 1])), np.float64(lml), np.asarray(trace)
+
+
+# ---------------------------------------------------------------------------------------
+# Leave-one-out cross-validation (GPML section 5.4.2): the second standard criterion for the hyper-parameters, more robust
+# than the LML when the model is misspecified.  gpmi_loo gives the per-point held-out predictions and their log
+# probability, gpmi_loo_grad its derivatives w.r.t. (l, sigma, noise_var); the reference has neither.
+# ---------------------------------------------------------------------------------------
+def compute_loo_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None):
+    """Leave-one-out log predictive probability, GPML eq. 5.11: the sibling of compute_mar_likelihood, with its argument
+    handling (X_test accepted and unused; l a scalar, a 1-element array or a d-vector of per-dimension lengthscales, which
+    do not outlive the call)."""
+    l, r = split_lengthscale(l)
+    ctx = ctx or default_context()
+    try:
+        ctx.fit(X_train, y_train, sigma, l, noise_var, lengthscales=r)
+        return np.float64(ctx.loo()[3])
+    finally:
+        if r is not None:
+            ctx.set_lengthscales(None)
+
+
+def loo_and_gradient(X_train, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None):
+    """(L_LOO, dL_LOO/dl, dL_LOO/dsigma, dL_LOO/dnoise_var) at (sigma, l, noise_var) with everything resident on the
+    device: the sibling of lml_and_gradient (GPML eqs. 5.11 and 5.13)."""
+    ctx = ctx or default_context()
+    ctx.fit(X_train, y_train, sigma, l, noise_var)
+    total = ctx.loo()[3]
+    dl, ds, dn = ctx.loo_grad()
+    return np.float64(total), dl, ds, dn
+
+
+def tune_hyperparms_loo(X_train, y_train, *, sigma=1.0, l=1.0, noise_var=NOISE_VAR, max_iter=100, tol=1e-6, ctx=None):
+    """Maximise the leave-one-out log predictive probability over (l, sigma, noise_var) by gradient ascent on their
+    logarithms, with the accept / halve / step-carry rule of tune_hyperparms_ard (the same loop).  Per-dimension
+    lengthscales the context carries are kept: l is then their common multiplier.
+
+    :return: (l, sigma, noise_var, loo, trace): the parameters reached, their L_LOO and the L_LOO of every accepted point,
+             the initial one first.  The context is left with the factorisation of the parameters reached.
+    """
+    from ._lib import scalar
+    ctx = ctx or default_context()
+    sigma, l, noise_var = scalar(sigma, "sigma"), scalar(l, "l"), scalar(noise_var, "noise_var")
+    if not (sigma > 0 and l > 0 and noise_var > 0):
+        raise ValueError("l, sigma and noise_var must be positive (the ascent runs on their logarithms)")
+    ctx.set_train(X_train, y_train)
+
+    def value(th):
+        p = np.exp(th)
+        try:
+            ctx.factorize(p[1], p[0], p[2])
+        except np.linalg.LinAlgError:
+            return -np.inf
+        return float(ctx.loo()[3])
+
+    theta, loo, trace = _log_ascent(value, lambda: np.asarray(ctx.loo_grad()), np.log([l, sigma, noise_var]), max_iter, tol)
+    p = np.exp(theta)
+    return float(p[0]), float(p[1]), float(p[2]), np.float64(loo), np.asarray(trace)

@@ -52,6 +52,7 @@ enum {
     GPMI_T_TRAIL_LAUNCHES = 10, /* number of trailing-update launches in last fit */
     GPMI_T_TRAIL_FLOPS = 11,    /* algorithmic flops of those launches: 2K per element on or below the diagonal, real rows + the y row */
     GPMI_T_GRAD = 12,     /* f2: L^-T, K_y^-1 and the fused gradient trace */
+    GPMI_T_LOO = 13,      /* gpmi_loo / gpmi_loo_grad: the whole device span of the last of the two */
     GPMI_T_COUNT = 16
 };
 
@@ -219,6 +220,26 @@ int gpmi_set_lengthscales(gpmi_ctx* ctx, const double* r, int64_t d);
  * Any output may be NULL.  sum_k r_k d_r[k] == l * d_ell (K depends on l * r_k only).  Refuses what gpmi_lml_grad
  * refuses.  One fused pass over K_y^-1 per 32 dimensions; the sums are bitwise reproducible from run to run. */
 int gpmi_lml_grad_ard(gpmi_ctx* ctx, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
+/* Leave-one-out cross-validation at the resident regression factorisation (Rasmussen & Williams, GPML, section 5.4.2,
+ * eqs. 5.10-5.12).  With K_y = K + noise_var I, alpha = K_y^-1 y and kappa_i = [K_y^-1]_ii:
+ *   mu[i]   = y_i - alpha_i / kappa_i,  var[i] = 1 / kappa_i      (mean and variance of y_i predicted from the other
+ *                                                                  N - 1 points, noise included)
+ *   logp[i] = -.5 log var_i - (y_i - mu_i)^2 / (2 var_i) - .5 log(2 pi)
+ *   *loo    = sum_i logp[i]                                       (added on the device in a fixed order)
+ * mu, var, logp: N doubles each; every output may be NULL.  Needs a resident regression factor: refused without one, and
+ * after a Laplace or softmax fit by the rule stated at gpmi_laplace_fit.  Every kernel kind (only L, m and y are read);
+ * with lengthscales set the factor is that of the scaled inputs, as everywhere.  The factor, m and any resident test
+ * state are left untouched.  Costs N^3/3 beyond the fit (U = L^-T; kappa_i = sum_j U_ij^2), half of gpmi_lml_grad. */
+int gpmi_loo(gpmi_ctx* ctx, double* mu, double* var, double* logp, double* loo);
+/* The derivatives of *loo (GPML eq. 5.13) w.r.t. l, sigma and noise_var at the resident factorisation:
+ *   d/dtheta = sum_i (alpha_i r_i - .5 (1 + alpha_i^2 / kappa_i) s_i) / kappa_i,
+ *   Z = K_y^-1 dK_y/dtheta,  r = Z alpha,  s_i = [Z K_y^-1]_ii
+ * with dK_y/dl = K o sqdist / l^3, dK_y/dsigma = 2 K / sigma, dK_y/dnoise_var = I.  Any output may be NULL.  Squared-
+ * exponential kernel only: refuses what gpmi_lml_grad refuses; state rules as gpmi_loo.  With lengthscales set, sqdist is
+ * that of the scaled inputs and d_ell the derivative w.r.t. the common multiplier l.  The l component takes the diagonal
+ * of K_y^-1 (K o sqdist) K_y^-1, a full N x N x N product (2 N^3 flops beside the 2 N^3 / 3 of gpmi_lml_grad), formed
+ * NB rows at a time; bitwise reproducible from run to run.  Device memory: DESIGN.md section 4c. */
+int gpmi_loo_grad(gpmi_ctx* ctx, double* d_ell, double* d_sigma, double* d_noise);
 /* The same two traces from the arguments gradient_ascent(a, b, sigma, l, alpha, K_y) receives
  * (tune_hyperparms_regression.py:31): a, b: N x d; alpha: N; K_y_inv: N x N row-major (host).
  * One fused N^2 pass instead of the reference's two N x N products (:55). */
