@@ -22,13 +22,14 @@ LIB_PATH = os.path.join(_HERE, "libgpmi355x.so")
 GPMI_OK, GPMI_ERR_NOT_PD, GPMI_ERR_BAD_ARG, GPMI_ERR_RUNTIME = 0, 1, 2, 3
 ABI_VERSION = 4
 SOFTMAX_MAX_CLASSES = 10     # GPMI_SOFTMAX_MAX_CLASSES of include/gpmi.h
+SPARSE_METHODS = {"vfe": 0, "fitc": 1}     # GPMI_SPARSE_VFE / GPMI_SPARSE_FITC
 
 # stage-timer slots (enum in gpmi.h)
 T_KBUILD, T_CHOL, T_CHOL_PANEL, T_CHOL_TRAIL, T_LML, T_KS, T_SOLVE_V, T_MEANVAR, \
     T_ALPHA, T_POSTCHOL, T_TRAIL_LAUNCHES, T_TRAIL_FLOPS = range(12)
 T_COUNT = 16
 TIMER_NAMES = ["kbuild", "chol", "chol_panel", "chol_trail", "lml", "ks", "solve_v", "meanvar",
-               "alpha", "postchol", "trail_launches", "trail_flops", "grad", "loo"]
+               "alpha", "postchol", "trail_launches", "trail_flops", "grad", "loo", "sparse"]
 
 _dp = C.POINTER(C.c_double)
 _i64 = C.c_int64
@@ -73,11 +74,15 @@ SIGNATURES = {
     "gpmi_softmax_fit": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int),
                          C.POINTER(C.c_int), _dp],
     "gpmi_softmax_predict_resident": [_vp, _dp, _dp, _i64, _dp, _dp],
+    "gpmi_sparse_fit": [_vp, _dp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(_i64)],
+    "gpmi_sparse_predict_resident": [_vp, _dp, _dp, C.c_int],
+    "gpmi_sparse_get": [_vp, _dp, _dp],
     "gpmi_get_timers": [_vp, _dp, C.c_int],
     "gpmi_sync": [_vp],
     "gpmi_probe_mfma_f64": [_vp, _dp],
     "gpmi_probe_mfma_f64_ex": [_vp, C.c_int, C.c_int, C.c_int, _dp],
     "gpmi_probe_gemm": [_vp, _i64, _i64, _i64, C.c_int, C.c_int, C.c_int, _dp],
+    "gpmi_probe_gram": [_vp, _i64, _i64, C.c_int, _dp],
     "gpmi_probe_hbm_write": [_vp, _i64, _dp],
     "gpmi_probe_hbm_ex": [_vp, _i64, C.c_int, C.c_int, _dp],
     "gpmi_device_info": [_vp, _dp, C.c_int],

@@ -301,7 +301,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (rc) return rc;
     hipStream_t s = c->stream;
     c->have_factor = false;
-    c->have_laplace = c->have_softmax = false;          // a regression factorisation replaces a resident Laplace or softmax fit
+    c->have_laplace = c->have_softmax = c->have_sparse = false;   // a regression factorisation replaces a resident Laplace or softmax fit
     c->v_in_A = false;
     c->have_vinv = false;
     c->have_vside = false;
@@ -423,10 +423,13 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
 // tri: V starts as the identity (m == Np), so at step k only rows < k + nb are non-zero in
 // block column k -- the sweep then costs Np^3/3 and leaves the upper triangular L^-T.
 hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri) {
+    return solve_sweep_factor(c, c->A.as<double>(), c->ldA, c->Np, V, ldv, m, tri);
+}
+
+hipError_t solve_sweep_factor(gpmi_ctx* c, const double* A, int64_t ld, int64_t Np, double* V, int64_t ldv, int64_t m,
+                              bool tri) {
     hipError_t e;
     hipStream_t sm = c->stream;
-    const double* A = c->A.as<double>();
-    const int64_t ld = c->ldA, Np = c->Np;
     const int64_t NB = c->block(Np);
     const bool la = c->lookahead && c->pstream && Np > NB && Np >= c->la_min;
     hipStream_t sp_ = la ? c->pstream : sm;

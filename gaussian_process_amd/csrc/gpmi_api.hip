@@ -76,7 +76,8 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow})
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
+                       &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -137,7 +138,7 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "ld_pad")) {
         if (value < 0 || value % 2) return fail_arg("ld_pad must be even and >= 0");
         c->ld_pad = value;
-        c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
+        c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
     } else if (!strcmp(name, "timing")) {
         c->timing = value ? 1 : 0;
     } else if (!strcmp(name, "lookahead")) {
@@ -154,6 +155,9 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "one_pass_form")) {
         if (value < 0 || value > 2) return fail_arg("one_pass_form must be 0 (by size), 1 (rows ride) or 2 (rows follow)");
         c->one_pass_form = (int)value;
+    } else if (!strcmp(name, "sparse_slab")) {
+        if (value < 0) return fail_arg("sparse_slab must be >= 0 (0: by size)");
+        c->sparse_slab = value;
     } else if (!strcmp(name, "lanes")) {
         if (value < 0 || value > 8) return fail_arg("lanes must be 0 (by size) .. 8");
         c->lanes = (int)value;
@@ -184,7 +188,7 @@ int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
     if (kind < 0 || kind > 2) return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear) or 2 (periodic)");
     if (kind == 2 && (!(p0 != 0.0) || !(p1 != 0.0))) return fail_arg("gpmi_set_kernel: period and lengthscale must be non-zero");
     c->kind = kind; c->kp0 = p0; c->kp1 = p1;
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
     return GPMI_OK;
 }
 
@@ -200,7 +204,7 @@ int gpmi_set_kernel_params(gpmi_ctx* c, int kind, const double* params, int npar
         return fail_arg("gpmi_set_kernel_params: theta_2, 4, 5, 7, 8, 10 divide and must be non-zero");
     c->kind = 3;
     for (int i = 0; i < 11; ++i) c->kpv[i] = params[i];
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
     return GPMI_OK;
 }
 
@@ -299,7 +303,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (!c || !X || !y) return fail_arg("gpmi_set_train: null argument");
     if (N <= 0 || d <= 0) return fail_arg("gpmi_set_train: N and d must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = c->have_softmax = false;
+    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = c->have_softmax = c->have_sparse = false;
     HIP_TRY(c->X.ensure((size_t)N * d * 8));
     HIP_TRY(c->y.ensure((size_t)N * 8));
     HIP_TRY(hipMemcpyAsync(c->X.p, X, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream));
@@ -324,7 +328,7 @@ int gpmi_set_lengthscales(gpmi_ctx* c, const double* r, int64_t d) {
     }
     HIP_TRY(hipSetDevice(c->device));
     // as a new training set: whatever was fitted belongs to the old covariance
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = false;
+    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
     c->post_in_A = c->post_in_P = false;
     if (r && d > 0) c->ard_r.assign(r, r + d);
     else c->ard_r.clear();
@@ -1094,6 +1098,26 @@ int gpmi_softmax_predict_resident(gpmi_ctx* c, double* mu, double* cov, int64_t 
     if (!c) return fail_arg("gpmi_softmax_predict: null context");
     HIP_TRY(hipSetDevice(c->device));
     return softmax_predict_impl(c, mu, cov, n_samples, normals, prob);
+}
+
+int gpmi_sparse_fit(gpmi_ctx* c, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,
+                    int method, double* value, int64_t* bad_pivot) {
+    if (!c || !Z) return fail_arg("gpmi_sparse_fit: null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    TuneScope tune_scope(&c->tune);
+    return sparse_fit_impl(c, Z, m, sigma, ell, noise_var, jitter, method, value, bad_pivot);
+}
+
+int gpmi_sparse_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
+    if (!c) return fail_arg("gpmi_sparse_predict: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return sparse_predict_impl(c, mu, out2, want_sd);
+}
+
+int gpmi_sparse_get(gpmi_ctx* c, double* c_out, double* q_out) {
+    if (!c) return fail_arg("gpmi_sparse_get: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return sparse_get_impl(c, c_out, q_out);
 }
 
 int gpmi_get_timers(gpmi_ctx* c, double* stage_ms, int count) {

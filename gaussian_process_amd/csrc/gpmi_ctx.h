@@ -190,6 +190,17 @@ struct gpmi_ctx {
     bool have_softmax = false;
     int sm_classes = 0;
     DevBuf sm, sm_part, sm_E, sm_B, sm_out;
+    // sparse regression with inducing points (sparse.hip): sp_L holds L = chol(K_uu + jitter I) (sp_mp x sp_ld), sp_B the
+    // factor L_B of B = I + A~ A~^T with c = L_B^-1 A~ y~ in its row sp_mp, sp_Z the (scaled) inducing inputs, sp_q the N
+    // values q_i, sp_W the slab workspace (sp_wrows x sp_ld) that prediction reuses for its chunks of test rows.  A and
+    // the regression state are not touched, but the rule above holds with one more flag: a sparse fit clears have_factor,
+    // have_laplace and have_softmax, and whatever clears have_factor clears have_sparse.
+    bool have_sparse = false;
+    int sp_method = 0, sp_fused = 1;
+    int64_t sparse_slab = 0;     // option "sparse_slab": training rows per slab (0 = by size), rounded up to 128
+    int64_t sp_m = 0, sp_mp = 0, sp_ld = 0, sp_wrows = 0;
+    Box boxU;                    // bounding box of the (scaled) inducing inputs
+    DevBuf sp_Zraw, sp_Z, sp_L, sp_B, sp_W, sp_q, sp_vec, sp_part, sp_scr, sp_info, sp_pred;
     // timers
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -259,6 +270,9 @@ struct SweepFollower {
 hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, int64_t nrows, int64_t* info,
                             bool account, int64_t carried_rows = 0, const SweepFollower* follow = nullptr);
 hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri = false);
+// the same sweep through any resident lower factor (ncols x ncols, leading dimension ld), not only the one in c->A
+hipError_t solve_sweep_factor(gpmi_ctx* c, const double* L, int64_t ld, int64_t ncols, double* V, int64_t ldv, int64_t m,
+                              bool tri = false);
 void set_kernel_args(const gpmi_ctx* c, RbfArgs& r);
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows = 0, bool test_cols = false);
 // with_test: the test set's rows K(X*, X) ride below the y rows (they come out as v^T = K_s^T L^-T, a7 inside a3) and
@@ -286,5 +300,16 @@ void laplace_quad_nodes(double sig2, int* M, double* T, double* h);
 int softmax_fit_impl(gpmi_ctx* c, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
                      int* iters, int* converged, double* f_hat);
 int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t n_samples, const double* normals, double* prob);
+
+// sparse.hip: sparse regression with m inducing inputs (VFE / FITC) in the whitened form, and its prediction
+int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,
+                    int method, double* value, int64_t* bad_pivot);
+int sparse_predict_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
+int sparse_get_impl(gpmi_ctx* c, double* c_out, double* q_out);
+// B_lower (mp x mp, leading dimension ldb) += V^T V for the row-major slab V (rows x mp, leading dimension ldv; rows and
+// mp multiples of 128) on the matrix pipe; part: gram_part_doubles(rows, mp) doubles of workspace
+int64_t gram_part_doubles(int64_t rows, int64_t mp);
+hipError_t launch_gram_tn(hipStream_t s, const double* V, int64_t ldv, int64_t rows, int64_t mp, double* part, double* B,
+                          int64_t ldb);
 
 }  // namespace gpmi

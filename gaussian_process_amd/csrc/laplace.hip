@@ -329,6 +329,7 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     c->have_factor = false;
     c->have_laplace = false;
     c->have_softmax = false;
+    c->have_sparse = false;
     c->v_in_A = false;
     c->have_vinv = false;
     c->have_vside = false;

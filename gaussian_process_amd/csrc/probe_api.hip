@@ -134,6 +134,43 @@ int gpmi_probe_gemm(gpmi_ctx* c, int64_t M, int64_t N, int64_t K, int lower, int
     return rc;
 }
 
+int gpmi_probe_gram(gpmi_ctx* c, int64_t S, int64_t m, int reps, double* out) {
+    if (!c || !out) return fail_arg("gpmi_probe_gram: null argument");
+    if (S <= 0 || m <= 0 || S % TILE || m % TILE || reps < 1) return fail_arg("gpmi_probe_gram: S%128 and m%128 must be 0");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int64_t ld = m + c->ld_pad;
+    DevBuf V, B, part;
+    int rc = GPMI_OK;
+    hipError_t e;
+    hipEvent_t ea = nullptr, eb = nullptr;
+    do {
+        if ((e = V.ensure((size_t)S * ld * 8)) != hipSuccess || (e = B.ensure((size_t)m * ld * 8)) != hipSuccess ||
+            (e = part.ensure((size_t)gram_part_doubles(S, m) * 8)) != hipSuccess) { rc = fail_runtime(e, "hipMalloc"); break; }
+        (void)hipMemsetAsync(B.p, 0, (size_t)m * ld * 8, s);
+        hipLaunchKernelGGL(probe_fill_random_kernel, dim3(8, (unsigned)std::min<int64_t>(S, 65535)), dim3(256), 0, s, V.as<double>(), ld, m, 0x1234ull);
+        if (S > 65535) (void)hipMemcpyAsync(V.as<double>() + 65535 * ld, V.p, (size_t)(S - 65535) * ld * 8, hipMemcpyDeviceToDevice, s);
+        e = launch_gram_tn(s, V.as<double>(), ld, S, m, part.as<double>(), B.as<double>(), ld);
+        (void)hipEventCreate(&ea); (void)hipEventCreate(&eb);
+        (void)hipEventRecord(ea, s);
+        for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_gram_tn(s, V.as<double>(), ld, S, m, part.as<double>(), B.as<double>(), ld);
+        (void)hipEventRecord(eb, s);
+        hipError_t e2 = hipEventSynchronize(eb);
+        if (e != hipSuccess) { rc = fail_runtime(e, "gram launch"); break; }
+        if (e2 != hipSuccess) { rc = fail_runtime(e2, "gram sync"); break; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ea, eb);
+        out[1] = ms / reps;
+        const double nt = (double)(m / TILE);
+        out[0] = 2.0 * (double)S * (nt * (nt + 1) / 2) * TILE * TILE / (out[1] * 1e-3) / 1e12;
+    } while (0);
+    if (ea) (void)hipEventDestroy(ea);
+    if (eb) (void)hipEventDestroy(eb);
+    (void)hipStreamSynchronize(s);
+    V.release(); B.release(); part.release();
+    return rc;
+}
+
 int gpmi_probe_hbm_ex(gpmi_ctx* c, int64_t bytes, int mode, int blocks, double* gbps) {
     if (!c || !gbps || bytes < 4096 || blocks < 1 || mode < 0 || mode > 6) return fail_arg("gpmi_probe_hbm_ex: bad argument");
     HIP_TRY(hipSetDevice(c->device));

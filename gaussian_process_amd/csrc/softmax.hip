@@ -492,6 +492,7 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     c->have_factor = false;
     c->have_laplace = false;
     c->have_softmax = false;
+    c->have_sparse = false;
     c->v_in_A = false;
     c->have_vinv = false;
     c->have_vside = false;

@@ -33,6 +33,20 @@ def softmax_labels(labels, n_classes=None):
     return lab, n_classes
 
 
+def sparse_args(X, Z, method):
+    """Host-side check of a sparse fit's arguments, before any device call: -> (X, Z as float64, the method's number).
+    method is "vfe" or "fitc"; Z is (m, d) with the training set's d and 1 <= m <= N."""
+    if method not in _lib.SPARSE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(_lib.SPARSE_METHODS), method))
+    X = as_f64(X, 2, "X_train")
+    Z = as_f64(Z, 2, "Z")
+    if Z.shape[1] != X.shape[1]:
+        raise ValueError("Z has d=%d but the training set has d=%d" % (Z.shape[1], X.shape[1]))
+    if not 1 <= Z.shape[0] <= X.shape[0]:
+        raise ValueError("the number of inducing inputs must be in 1..N = %d, got %d" % (X.shape[0], Z.shape[0]))
+    return X, Z, _lib.SPARSE_METHODS[method]
+
+
 KEEP = object()      # lengthscales=KEEP: leave the context's per-dimension lengthscales as they are
 
 
@@ -101,6 +115,12 @@ class GPContext:
         """-> (TFLOP/s, ms per launch) of the trailing-update GEMM kernel on scratch buffers"""
         out = np.zeros(2)
         check(self._lib.gpmi_probe_gemm(self._h, M, N, K, lower, variant, reps, ptr(out)))
+        return tuple(out)
+
+    def probe_gram(self, S, m, reps=3):
+        """-> (TFLOP/s, ms per call) of the sparse fit's Gram accumulation B += V^T V on a random S x m slab"""
+        out = np.zeros(2)
+        check(self._lib.gpmi_probe_gram(self._h, int(S), int(m), int(reps), ptr(out)))
         return tuple(out)
 
     def device_info(self):
@@ -436,6 +456,38 @@ class GPContext:
         check(self._lib.gpmi_softmax_predict_resident(self._h, ptr(mu), ptr(cov), S, ptr(z) if S else None,
                                                       ptr(prob) if S else None))
         return mu, cov, prob
+
+    # ---- sparse regression with inducing points (VFE / FITC) ------------------------------
+    def sparse_fit(self, X, y, Z, sigma, l, noise_var, *, method="vfe", jitter=1e-6, lengthscales=KEEP):
+        """Sparse GP regression with the m inducing inputs Z (m, d), m <= N (gpmi_sparse_fit): O(N m^2) work and
+        O(m^2 + N d) device memory, for N far beyond an N x N covariance.  method "vfe" returns Titsias' collapsed lower
+        bound of the log marginal likelihood, "fitc" the log likelihood log N(y | 0, Q_ff + diag(K_ff - Q_ff) + noise I).
+        jitter is added to the diagonal of K(Z, Z).  The factors stay on the device for sparse_predict."""
+        X, Z, method_id = sparse_args(X, Z, method)
+        self._set_train_ard(X, y, lengthscales)
+        val = C.c_double()
+        bad = C.c_int64()
+        st = self._lib.gpmi_sparse_fit(self._h, ptr(Z), Z.shape[0], scalar(sigma, "sigma"), scalar(l, "l"),
+                                       scalar(noise_var, "noise_var"), float(jitter), method_id,
+                                       C.byref(val), C.byref(bad))
+        check(st, bad.value)
+        self.m_inducing = Z.shape[0]
+        return val.value
+
+    def sparse_predict(self, Xs, want_sd=True):
+        """(mu, sd or var) of the latent function at Xs from the resident sparse fit (gpmi_sparse_predict_resident)."""
+        self.set_test(Xs)
+        mu = np.empty(self.n)
+        o2 = np.empty(self.n)
+        check(self._lib.gpmi_sparse_predict_resident(self._h, ptr(mu), ptr(o2), 1 if want_sd else 0))
+        return mu, o2
+
+    def sparse_state(self):
+        """(c (m,), q (N,)) of the resident sparse fit: c = L_B^-1 A~ y~ and q_i = |L^-1 k_u(x_i)|^2 (gpmi_sparse_get)."""
+        c = np.empty(int(getattr(self, "m_inducing", 0)))
+        q = np.empty(self.N)
+        check(self._lib.gpmi_sparse_get(self._h, ptr(c), ptr(q)))
+        return c, q
 
     # ---- batched LML ----------------------------------------------------------------
     def lml_batch(self, triples):

@@ -53,6 +53,7 @@ enum {
     GPMI_T_TRAIL_FLOPS = 11,    /* algorithmic flops of those launches: 2K per element on or below the diagonal, real rows + the y row */
     GPMI_T_GRAD = 12,     /* f2: L^-T, K_y^-1 and the fused gradient trace */
     GPMI_T_LOO = 13,      /* gpmi_loo / gpmi_loo_grad: the whole device span of the last of the two */
+    GPMI_T_SPARSE = 14,   /* gpmi_sparse_fit: the whole device span of the last sparse fit */
     GPMI_T_COUNT = 16
 };
 
@@ -75,6 +76,8 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
  *               sweep, 2 half width over the last blocks, 4 quarter width for the last one, bits 4.. = how many blocks
  *               count as "last" (0: three), when "nb" is automatic.  Until round 2 any non-zero value meant "up and
  *               down": that is 3 now; other bits or a negative value are refused),
+ *               "sparse_slab" (gpmi_sparse_fit: training rows per slab, rounded up to 128; 0 = by size (16384).  It bounds
+ *               the slab workspace to that many rows of m + "ld_pad" doubles whatever N is; same results to rounding),
  *               "shallow_min" (under lookahead, panels with fewer columns left than this use the one-launch panel
  *               kernels: the update they would run beside is over long before they are; default 6144, 0 = never),
  *               "slack_forms" (a Cholesky of 49152 columns and more, whose lookahead panel chain is far off the critical
@@ -305,6 +308,44 @@ int gpmi_softmax_fit(gpmi_ctx* ctx, int n_classes, double sigma, double ell, dou
 int gpmi_softmax_predict_resident(gpmi_ctx* ctx, double* mu, double* cov, int64_t n_samples, const double* normals,
                                   double* prob);
 
+/* Sparse GP regression with m inducing inputs Z (m x d, d as in gpmi_set_train) on the resident training set, for N far
+ * beyond an N x N covariance: O(N m^2) flops, O(m^2 + N d) device memory.  GPML chapter 8; the
+ * collapsed bound of Titsias (2009) -- method GPMI_SPARSE_VFE -- and FITC of Snelson & Ghahramani (2006).  Squared-
+ * exponential kernel only (kind 0; sigma, ell as gpmi_factorize, the context's lengthscales apply to X, Z and the test
+ * set alike), s = noise_var > 0, jitter >= 0 added to the diagonal of K_uu.  In the whitened form
+ *   L = chol(K_uu + jitter I),  A = L^-1 K_uf (m x N),  q_i = |A[:, i]|^2,
+ *   Lambda_i = s (VFE)  or  s + sigma^2 - q_i (FITC),  A~ = A Lambda^-1/2,  y~ = Lambda^-1/2 y,
+ *   B = I + A~ A~^T,  L_B = chol(B),  c = L_B^-1 A~ y~,
+ *   *value = -N/2 log 2 pi - sum log diag L_B - 1/2 sum_i log Lambda_i - 1/2 y~^T y~ + 1/2 c^T c
+ *            [VFE only: - sum_i (sigma^2 - q_i) / (2 s)]
+ * which for VFE is a lower bound of the log marginal likelihood gpmi_factorize returns and for FITC is
+ * log N(y | 0, Q_ff + Lambda), Q_ff = K_fu K_uu^-1 K_uf.  K_uf is never held: the training rows pass in slabs (option
+ * "sparse_slab") through the cross-covariance build, the sweep through L, one row pass and the accumulation of B; every
+ * sum runs in a fixed order (bitwise reproducible from run to run at one slab size).
+ *   GPMI_ERR_BAD_ARG: m < 1, m > N, noise_var <= 0, jitter < 0, an unknown method, a kernel kind other than 0.
+ *   GPMI_ERR_NOT_PD:  a pivot of K_uu + jitter I (*bad_pivot = its 1-based index), a Lambda_i of FITC that is not a
+ *                     positive finite number (*bad_pivot = the 1-based training row), a pivot of B (*bad_pivot = m + its
+ *                     1-based index).
+ * L, L_B, c, Z and the hyper-parameters stay resident.  A sparse fit is not a regression factor: it takes the place of a
+ * resident regression factor, Laplace or softmax fit under the rule stated at gpmi_laplace_fit -- gpmi_predict*,
+ * gpmi_get_alpha, gpmi_post_*, gpmi_lml_grad* and gpmi_loo* refuse (GPMI_ERR_BAD_ARG) until the next regression
+ * factorisation; that, a Laplace or softmax fit, gpmi_set_train and gpmi_set_lengthscales drop it.  value / bad_pivot may
+ * be NULL.  Timers: GPMI_T_SPARSE the whole span, of which GPMI_T_KS the cross-covariance builds, GPMI_T_SOLVE_V the
+ * sweeps through L, GPMI_T_MEANVAR the row pass with g = A~ y~, GPMI_T_POSTCHOL the accumulation of A~ A~^T and
+ * GPMI_T_CHOL the two factorisations. */
+#define GPMI_SPARSE_VFE 0
+#define GPMI_SPARSE_FITC 1
+int gpmi_sparse_fit(gpmi_ctx* ctx, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,
+                    int method, double* value, int64_t* bad_pivot);
+/* Prediction on the resident test set (gpmi_set_test) from the resident sparse fit:
+ *   v1 = L^-1 k_u*,  v2 = L_B^-1 v1,  mu = v2^T c,  var = sigma^2 - |v1|^2 + |v2|^2
+ * -- the variance of the latent f, the convention of gpmi_predict_resident; out2 = sqrt(var) if want_sd (NaN where var is
+ * negative) else var.  mu, out2: n doubles each, either may be NULL.  The test rows pass in chunks of the fit's slab size.
+ * Refused (GPMI_ERR_BAD_ARG) without a sparse fit or a test set. */
+int gpmi_sparse_predict_resident(gpmi_ctx* ctx, double* mu, double* out2, int want_sd);
+/* c (m doubles) and q (N doubles) of the resident sparse fit; either may be NULL.  For tests and small N. */
+int gpmi_sparse_get(gpmi_ctx* ctx, double* c_out, double* q_out);
+
 int gpmi_get_timers(gpmi_ctx* ctx, double* stage_ms, int count);
 /* block the host until everything queued on the context has finished */
 int gpmi_sync(gpmi_ctx* ctx);
@@ -321,6 +362,9 @@ int gpmi_probe_mfma_f64_ex(gpmi_ctx* ctx, int blocks_per_cu, int nacc, int iters
  * ablation bits (0 = the production kernel); out[0] = TFLOP/s, out[1] = ms per launch */
 int gpmi_probe_gemm(gpmi_ctx* ctx, int64_t M, int64_t N, int64_t K, int lower, int variant, int reps,
                     double* out);
+/* the Gram accumulation of gpmi_sparse_fit alone, B_lower (m x m) += V^T V for a random row-major slab V (S x m), split
+ * launch and reduction together; out[0] = TFLOP/s on the 128 x 128 tiles it computes (2 S per element), out[1] = ms */
+int gpmi_probe_gram(gpmi_ctx* ctx, int64_t S, int64_t m, int reps, double* out);
 /* streaming-store bandwidth (GB/s) over `bytes` of device memory */
 int gpmi_probe_hbm_write(gpmi_ctx* ctx, int64_t bytes, double* gbps);
 /* streaming bandwidth with a chosen access form: mode 0 grid-stride 16-byte stores, 1 the same
