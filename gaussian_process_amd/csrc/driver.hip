@@ -231,10 +231,31 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
     return hipSuccess;
 }
 
-void set_kernel_args(const gpmi_ctx* c, RbfArgs& r) {
+RbfArgs rbf_cross(const gpmi_ctx* c, const double* A, int64_t nA, const Box& ba, const double* B, int64_t nB, const Box& bb,
+                  int64_t row0, int64_t nrows, int64_t ncols, double* out, int64_t ld) {
+    RbfArgs r;
+    r.A = A; r.B = B;
+    r.nA = nA; r.nB = nB; r.d = c->d; r.row0 = row0; r.nrows = nrows; r.ncols = ncols;
     r.coef = c->coef; r.sig2 = c->sig2;
     r.kind = c->kind; r.kp0 = c->kp0; r.kp1 = c->kp1;
     for (int i = 0; i < 11; ++i) r.kpv[i] = c->kpv[i];
+    r.diag_add = 0.; r.symmetric = 0;
+    // kernel_4's delta is eye whenever the matrix is square (CO2_example.py:58): the test set against the training set
+    r.delta_square = (A == c->x_test() && B == c->x_train() && nA == nB) ? 1 : 0;
+    r.max_sq = box_max_sq(ba, bb);
+    r.out = out; r.ld = ld;
+    return r;
+}
+
+RbfArgs rbf_sym(const gpmi_ctx* c, const double* X, int64_t n, const Box& box, double diag_add, int64_t npad, double* out,
+                int64_t ld) {
+    RbfArgs r = rbf_cross(c, X, n, box, X, n, box, 0, npad, npad, out, ld);
+    r.diag_add = diag_add; r.symmetric = 1; r.delta_square = 1;
+    return r;
+}
+
+RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld) {
+    return rbf_cross(c, c->x_test(), c->n, c->box_test(), c->x_train(), c->N, c->box_train(), 0, c->np_, c->Np, out, ld);
 }
 
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows, bool test_cols) {
@@ -242,7 +263,6 @@ int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows, bool test_cols) {
     c->ldA = c->Np + (test_cols ? test_rows : 0) + c->ld_pad;
     c->Mp = c->Np + TILE + test_rows;
     c->yrow = test_cols ? c->Np + test_rows : c->Np;         // with their own columns the test rows come BEFORE the y rows
-    c->post_in_A = false;
     HIP_TRY(c->A.ensure((size_t)c->Mp * c->ldA * sizeof(double)));
     HIP_TRY(c->info.ensure(sizeof(int64_t)));
     HIP_TRY(c->red.ensure(16 * sizeof(double)));
@@ -276,7 +296,7 @@ void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, doub
 // K build + Cholesky (+ forward solve through the y row) + LML on the stream
 int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, double* lml,
                    int64_t* bad_pivot, bool with_test, double* mu, double* out2, int want_sd, bool with_post, double jitter) {
-    if (!c->have_train) return fail_arg("gpmi_factorize: no training set (call gpmi_set_train)");
+    if (!c->res.have_train) return fail_arg("gpmi_factorize: no training set (call gpmi_set_train)");
     if (c->kind == 0 && (!(ell != 0.0) || std::isnan(ell) || std::isnan(sigma)))
         return fail_arg("gpmi_factorize: ell must be non-zero and hyper-parameters finite");
     if (std::isnan(noise_var)) return fail_arg("gpmi_factorize: noise_var is NaN");
@@ -297,15 +317,10 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
         }
     }
     if (with_post && std::isnan(jitter)) return fail_arg("gpmi_fit_predict_sample: jitter is NaN");
+    c->res.drop_fit();                // a regression factorisation replaces whatever fit was resident
     int rc = ensure_train_buffers(c, with_test ? c->np_ : 0, form == 3);
     if (rc) return rc;
     hipStream_t s = c->stream;
-    c->have_factor = false;
-    c->have_laplace = c->have_softmax = c->have_sparse = false;   // a regression factorisation replaces a resident Laplace or softmax fit
-    c->v_in_A = false;
-    c->have_vinv = false;
-    c->have_vside = false;
-    c->have_v = false;
     c->timers_reset({GPMI_T_KBUILD, GPMI_T_CHOL, GPMI_T_CHOL_PANEL, GPMI_T_CHOL_TRAIL, GPMI_T_LML,
                      GPMI_T_TRAIL_LAUNCHES, GPMI_T_TRAIL_FLOPS});
     if (with_test) c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
@@ -317,13 +332,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, s));
 
     size_t sp = c->span_begin(GPMI_T_KBUILD);
-    RbfArgs r;
-    r.A = r.B = c->x_train();
-    r.nA = r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = c->Np; r.ncols = c->Np;
-    set_kernel_args(c, r);
-    r.diag_add = noise_var; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->box_train(), c->box_train());
-    r.out = A; r.ld = c->ldA;
+    const RbfArgs r = rbf_sym(c, c->x_train(), c->N, c->box_train(), noise_var, c->Np, A, c->ldA);
     HIP_TRY(launch_rbf(s, r));
     c->span_end(sp);                  // GPMI_T_KBUILD is the kernel-matrix build (a1 + a2) alone
     // the augmented rows: y then zeros (a4 rides in the factorisation)
@@ -334,23 +343,10 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     double* Vr = A + c->v_row0 * c->ldA;
     if (with_test) {                  // K(X*, X) below the y rows (a1 for K_s, GP_regression.py:127): they leave as v^T
         sp = c->span_begin(GPMI_T_KS);
-        RbfArgs t;
-        t.A = c->x_test(); t.B = c->x_train();
-        t.nA = c->n; t.nB = c->N; t.d = c->d; t.row0 = 0; t.nrows = c->np_; t.ncols = c->Np;
-        set_kernel_args(c, t);
-        t.diag_add = 0.; t.symmetric = 0;
-        t.delta_square = (c->n == c->N) ? 1 : 0;
-        t.max_sq = box_max_sq(c->box_test(), c->box_train());
-        t.out = Vr; t.ld = c->ldA;
+        const RbfArgs t = rbf_test_train(c, Vr, c->ldA);
         HIP_TRY(launch_rbf(s, t));
         if (form == 3) {              // K_ss + jitter I in the rows' own columns, lower tiles (GP_regression.py:128, 154)
-            RbfArgs q;
-            q.A = q.B = c->x_test();
-            q.nA = q.nB = c->n; q.d = c->d; q.row0 = 0; q.nrows = c->np_; q.ncols = c->np_;
-            set_kernel_args(c, q);
-            q.diag_add = jitter; q.symmetric = 1; q.delta_square = 1;
-            q.max_sq = box_max_sq(c->box_test(), c->box_test());
-            q.out = Vr + c->Np; q.ld = c->ldA;
+            const RbfArgs q = rbf_sym(c, c->x_test(), c->n, c->box_test(), jitter, c->np_, Vr + c->Np, c->ldA);
             HIP_TRY(launch_rbf(s, q));
         }
         c->span_end(sp);
@@ -403,15 +399,11 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (bad_pivot) *bad_pivot = 0;
     // tune_hyperparms_regression.py:312, with y^T alpha = m^T m
     if (lml) *lml = -.5 * red[1] - red[0] - (double)c->N / 2.0 * std::log(2 * M_PI);
-    c->have_factor = true;
-    c->factor_fused = tuning().panel_fused;
+    c->res.factor_replaced(tuning().panel_fused);
+    c->res.fit_done(Fit::Regression);
     if (with_test) {
-        c->v_in_A = true;
         c->ldV = c->ldA;
-        c->have_v = true;
-        ++c->v_gen;
-        c->post_in_A = form == 3;
-        c->post_jitter = jitter;
+        c->res.v_in_rows_of_A(form == 3, jitter);
         meanvar_to_host(c, h, mu, out2, want_sd);
     }
     return GPMI_OK;

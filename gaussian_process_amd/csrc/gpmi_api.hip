@@ -138,7 +138,7 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "ld_pad")) {
         if (value < 0 || value % 2) return fail_arg("ld_pad must be even and >= 0");
         c->ld_pad = value;
-        c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
+        c->res.drop_fit();
     } else if (!strcmp(name, "timing")) {
         c->timing = value ? 1 : 0;
     } else if (!strcmp(name, "lookahead")) {
@@ -188,7 +188,7 @@ int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
     if (kind < 0 || kind > 2) return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear) or 2 (periodic)");
     if (kind == 2 && (!(p0 != 0.0) || !(p1 != 0.0))) return fail_arg("gpmi_set_kernel: period and lengthscale must be non-zero");
     c->kind = kind; c->kp0 = p0; c->kp1 = p1;
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
+    c->res.drop_fit();
     return GPMI_OK;
 }
 
@@ -204,7 +204,7 @@ int gpmi_set_kernel_params(gpmi_ctx* c, int kind, const double* params, int npar
         return fail_arg("gpmi_set_kernel_params: theta_2, 4, 5, 7, 8, 10 divide and must be non-zero");
     c->kind = 3;
     for (int i = 0; i < 11; ++i) c->kpv[i] = params[i];
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
+    c->res.drop_fit();
     return GPMI_OK;
 }
 
@@ -303,7 +303,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (!c || !X || !y) return fail_arg("gpmi_set_train: null argument");
     if (N <= 0 || d <= 0) return fail_arg("gpmi_set_train: N and d must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    c->have_train = c->have_factor = c->have_v = c->have_test = c->have_laplace = c->have_softmax = c->have_sparse = false;
+    c->res.drop_train();
     HIP_TRY(c->X.ensure((size_t)N * d * 8));
     HIP_TRY(c->y.ensure((size_t)N * 8));
     HIP_TRY(hipMemcpyAsync(c->X.p, X, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream));
@@ -314,7 +314,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (c->ard() && (int64_t)c->ard_r.size() != d) c->ard_r.clear();    // another d: back to isotropic
     int rc = ard_rescale_train(c);
     if (rc) return rc;
-    c->have_train = true;
+    c->res.train_set();
     return GPMI_OK;
 }
 
@@ -322,22 +322,21 @@ int gpmi_set_lengthscales(gpmi_ctx* c, const double* r, int64_t d) {
     if (!c) return fail_arg("gpmi_set_lengthscales: null context");
     if (d < 0) return fail_arg("gpmi_set_lengthscales: d < 0");
     if (r && d > 0) {
-        if (c->have_train && d != c->d) return fail_arg("gpmi_set_lengthscales: d differs from the resident training set's");
+        if (c->res.have_train && d != c->d) return fail_arg("gpmi_set_lengthscales: d differs from the resident training set's");
         for (int64_t k = 0; k < d; ++k)
             if (!std::isfinite(r[k]) || !(r[k] > 0.0)) return fail_arg("gpmi_set_lengthscales: every lengthscale must be finite and > 0");
     }
     HIP_TRY(hipSetDevice(c->device));
     // as a new training set: whatever was fitted belongs to the old covariance
-    c->have_factor = c->have_v = c->have_laplace = c->have_softmax = c->have_sparse = false;
-    c->post_in_A = c->post_in_P = false;
+    c->res.drop_fit();
     if (r && d > 0) c->ard_r.assign(r, r + d);
     else c->ard_r.clear();
     if (!c->ard()) return GPMI_OK;
     HIP_TRY(c->ard_rdev.ensure((size_t)d * 8));
     HIP_TRY(hipMemcpyAsync(c->ard_rdev.p, c->ard_r.data(), (size_t)d * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int rc = c->have_train ? ard_rescale_train(c) : GPMI_OK;
-    if (rc == GPMI_OK && c->have_train && c->have_test) rc = ard_rescale_test(c);
+    int rc = c->res.have_train ? ard_rescale_train(c) : GPMI_OK;
+    if (rc == GPMI_OK && c->res.have_train && c->res.have_test) rc = ard_rescale_test(c);
     return rc;
 }
 
@@ -358,7 +357,7 @@ int gpmi_fit(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const double* y
 
 int gpmi_get_m(gpmi_ctx* c, double* m_out) {
     if (!c || !m_out) return fail_arg("gpmi_get_m: null argument");
-    if (!c->have_factor) return fail_arg("gpmi_get_m: no factorisation resident");
+    if (!c->res.regression()) return fail_arg("gpmi_get_m: no factorisation resident");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(m_out, c->m_row(), (size_t)c->N * 8,
                            hipMemcpyDeviceToHost, c->stream));
@@ -368,7 +367,7 @@ int gpmi_get_m(gpmi_ctx* c, double* m_out) {
 
 int gpmi_get_diag(gpmi_ctx* c, double* diag_out) {
     if (!c || !diag_out) return fail_arg("gpmi_get_diag: null argument");
-    if (!c->have_factor) return fail_arg("gpmi_get_diag: no factorisation resident");
+    if (!c->res.regression()) return fail_arg("gpmi_get_diag: no factorisation resident");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpy2DAsync(diag_out, 8, c->A.p, (size_t)(c->ldA + 1) * 8, 8, (size_t)c->N,
                              hipMemcpyDeviceToHost, c->stream));
@@ -378,7 +377,7 @@ int gpmi_get_diag(gpmi_ctx* c, double* diag_out) {
 
 int gpmi_get_factor_block(gpmi_ctx* c, int64_t r0, int64_t r1, int64_t c0, int64_t c1, double* out) {
     if (!c || !out) return fail_arg("gpmi_get_factor_block: null argument");
-    if (!c->have_factor) return fail_arg("gpmi_get_factor_block: no factorisation resident");
+    if (!c->res.regression()) return fail_arg("gpmi_get_factor_block: no factorisation resident");
     if (r0 < 0 || c0 < 0 || r1 > c->N || c1 > c->N || r0 > r1 || c0 > c1)
         return fail_arg("gpmi_get_factor_block: block out of range");
     if (r0 == r1 || c0 == c1) return GPMI_OK;
@@ -420,11 +419,10 @@ hipError_t gpmi::backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
     if (!mode) return launch_trsv_lt_fused(c->stream, A, c->ldA, b, xout, c->Np);
     hipError_t e;
     if (mode >= 2 && (e = c->vside.ensure((size_t)c->Np * 128 * 8)) != hipSuccess) return e;
-    if (!c->have_vinv || (mode >= 2 && !c->have_vside)) {
+    if (!c->res.have_vinv || (mode >= 2 && !c->res.have_vside)) {
         e = launch_vinv128(c->stream, A, c->ldA, c->Np, mode >= 2 ? c->vside.as<double>() : nullptr);
         if (e != hipSuccess) return e;
-        c->have_vinv = true;
-        c->have_vside = mode >= 2;
+        c->res.block_inverses_made(mode >= 2);
     }
     if (mode >= 2) {
         if ((e = c->flag.ensure(64)) != hipSuccess) return e;
@@ -434,31 +432,32 @@ hipError_t gpmi::backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
     return launch_trsv_lt_vinv(c->stream, A, c->ldA, b, xout, c->Np);
 }
 
+hipError_t gpmi::backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out) {
+    // padded tail of m is zero (identity padding), so the padded system stays consistent
+    hipError_t e = hipMemcpyAsync(x2, c->m_row(), (size_t)c->Np * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) return e;
+    *x_out = c->res.factor_fused ? x2 + c->Np : x2;
+    if (c->res.factor_fused) return backward_solve_fused(c, x2, x2 + c->Np);
+    return launch_trsv_lt(c->stream, c->A.as<double>(), c->ldA, x2, c->Np);
+}
+
 extern "C" {
 
 int gpmi_get_alpha(gpmi_ctx* c, double* alpha_out) {
     if (!c || !alpha_out) return fail_arg("gpmi_get_alpha: null argument");
-    if (!c->have_factor) return fail_arg("gpmi_get_alpha: no factorisation resident");
+    if (!c->res.regression()) return fail_arg("gpmi_get_alpha: no factorisation resident");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
     hipStream_t s = c->stream;
     c->timers_reset({GPMI_T_ALPHA});
     HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
     double* x = c->vec.as<double>();
-    // padded tail of m is zero (identity padding), so the padded system stays consistent
-    HIP_TRY(hipMemcpyAsync(x, c->m_row(), (size_t)c->Np * 8,
-                           hipMemcpyDeviceToDevice, s));
     size_t sp = c->span_begin(GPMI_T_ALPHA);
-    if (c->factor_fused) {
-        HIP_TRY(backward_solve_fused(c, x, x + c->Np));
-        x += c->Np;
-    } else {
-        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), c->ldA, x, c->Np));
-    }
+    HIP_TRY(backward_solve_resident(c, x, &x));
     c->span_end(sp);
     HIP_TRY(hipMemcpyAsync(alpha_out, x, (size_t)c->N * 8, hipMemcpyDeviceToHost, s));
     int gave_up = 0;
-    if (c->factor_fused && tuning().trsv_vinv >= 2)
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
         HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
@@ -468,10 +467,10 @@ int gpmi_get_alpha(gpmi_ctx* c, double* alpha_out) {
 
 int gpmi_set_test(gpmi_ctx* c, const double* Xs, int64_t n) {
     if (!c || !Xs) return fail_arg("gpmi_set_test: null argument");
-    if (!c->have_train) return fail_arg("gpmi_set_test: set the training set first");
+    if (!c->res.have_train) return fail_arg("gpmi_set_test: set the training set first");
     if (n <= 0) return fail_arg("gpmi_set_test: n must be positive");
     HIP_TRY(hipSetDevice(c->device));
-    c->have_test = c->have_v = false;
+    c->res.drop_test();
     HIP_TRY(c->Xs.ensure((size_t)n * c->d * 8));
     HIP_TRY(hipMemcpyAsync(c->Xs.p, Xs, (size_t)n * c->d * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -481,36 +480,27 @@ int gpmi_set_test(gpmi_ctx* c, const double* Xs, int64_t n) {
     c->np_ = round_up(n, TILE);
     int rc = ard_rescale_test(c);
     if (rc) return rc;
-    c->have_test = true;
+    c->res.test_set();
     return GPMI_OK;
 }
 
 int gpmi_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
     if (!c) return fail_arg("gpmi_predict: null context");
-    if (!c->have_factor) return fail_arg("gpmi_predict: no factorisation resident (call gpmi_factorize)");
-    if (!c->have_test) return fail_arg("gpmi_predict: no test set (call gpmi_set_test)");
+    if (!c->res.regression()) return fail_arg("gpmi_predict: no factorisation resident (call gpmi_factorize)");
+    if (!c->res.have_test) return fail_arg("gpmi_predict: no test set (call gpmi_set_test)");
     HIP_TRY(hipSetDevice(c->device));
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;      // solve with the kind of leaves that produced the resident factor
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
     c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
-    c->have_v = false;
-    c->v_in_A = false;
+    c->res.drop_v();
     c->ldV = c->Np + c->ld_pad;
     HIP_TRY(c->V.ensure((size_t)c->np_ * c->ldV * 8));
     HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
     double* V = c->V.as<double>();
 
     size_t sp = c->span_begin(GPMI_T_KS);
-    RbfArgs r;
-    r.A = c->x_test(); r.B = c->x_train();
-    r.nA = c->n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = c->np_; r.ncols = c->Np;
-    set_kernel_args(c, r);
-    r.diag_add = 0.; r.symmetric = 0;
-    r.delta_square = (c->n == c->N) ? 1 : 0;   // kernel_4's delta is eye whenever the matrix is square (CO2_example.py:58)
-    r.max_sq = box_max_sq(c->box_test(), c->box_train());
-    r.out = V; r.ld = c->ldV;
+    const RbfArgs r = rbf_test_train(c, V, c->ldV);
     HIP_TRY(launch_rbf(s, r));
     c->span_end(sp);
 
@@ -528,8 +518,7 @@ int gpmi_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
     HIP_TRY(hipMemcpyAsync(h.data(), dot, h.size() * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
-    c->have_v = true;
-    ++c->v_gen;
+    c->res.v_computed();
     meanvar_to_host(c, h, mu, out2, want_sd);
     return GPMI_OK;
 }
@@ -542,7 +531,7 @@ int gpmi_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
 int gpmi_fit_predict_resident(gpmi_ctx* c, double sigma, double ell, double noise_var, double* lml, int64_t* bad_pivot,
                               double* mu, double* out2, int want_sd) {
     if (!c) return fail_arg("gpmi_fit_predict: null context");
-    if (!c->have_test) return fail_arg("gpmi_fit_predict: no test set (call gpmi_set_test)");
+    if (!c->res.have_test) return fail_arg("gpmi_fit_predict: no test set (call gpmi_set_test)");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
     return factorize_impl(c, sigma, ell, noise_var, lml, bad_pivot, true, mu, out2, want_sd);
@@ -557,7 +546,7 @@ int gpmi_fit_predict_resident(gpmi_ctx* c, double sigma, double ell, double nois
 int gpmi_fit_predict_sample_resident(gpmi_ctx* c, double sigma, double ell, double noise_var, double jitter, double* lml,
                                      int64_t* bad_pivot, double* mu, double* out2, int want_sd, double* L_out) {
     if (!c) return fail_arg("gpmi_fit_predict_sample: null context");
-    if (!c->have_test) return fail_arg("gpmi_fit_predict_sample: no test set (call gpmi_set_test)");
+    if (!c->res.have_test) return fail_arg("gpmi_fit_predict_sample: no test set (call gpmi_set_test)");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
     int rc = factorize_impl(c, sigma, ell, noise_var, lml, bad_pivot, true, mu, out2, want_sd, true, jitter);
@@ -582,15 +571,7 @@ static int grad_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, s
     HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
     *span = c->span_begin(slot);
     // alpha = L^-T m (a5)
-    double* alpha = c->vec.as<double>();
-    HIP_TRY(hipMemcpyAsync(alpha, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, s));
-    if (c->factor_fused) {
-        HIP_TRY(backward_solve_fused(c, alpha, alpha + Np));
-        alpha += Np;
-    } else {
-        HIP_TRY(launch_trsv_lt(s, c->A.as<double>(), ld, alpha, Np));
-    }
-    *alpha_out = alpha;
+    HIP_TRY(backward_solve_resident(c, c->vec.as<double>(), alpha_out));
     // U = I * L^-T
     double* U = c->U.as<double>();
     HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
@@ -620,11 +601,10 @@ static int grad_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, s
 // non-zero column range (N^3/3), then one fused pass for the trace (grad.hip).
 int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     if (!c || !d_ell || !d_sigma) return fail_arg("gpmi_lml_grad: null argument");
-    if (!c->have_factor) return fail_arg("gpmi_lml_grad: no factorisation resident (call gpmi_factorize)");
+    if (!c->res.regression()) return fail_arg("gpmi_lml_grad: no factorisation resident (call gpmi_factorize)");
     if (c->kind != 0) return fail_arg("gpmi_lml_grad: squared-exponential kernel only (tune_hyperparms_regression.py:54)");
     HIP_TRY(hipSetDevice(c->device));
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
     const int64_t ld = c->ldA;
@@ -650,7 +630,7 @@ int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     std::vector<double> part((size_t)nblk * 2);
     HIP_TRY(hipMemcpyAsync(part.data(), a.partial, part.size() * 8, hipMemcpyDeviceToHost, s));
     int gave_up = 0;      // the one-launch backward solve's "a poll gave up" word, as gpmi_get_alpha reads it
-    if (c->factor_fused && tuning().trsv_vinv >= 2)
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
         HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
@@ -667,11 +647,10 @@ int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
 // gpmi_lml_grad; the per-block partials are summed on the device in a fixed order (at N = 65536 they are tens of MB).
 int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise) {
     if (!c) return fail_arg("gpmi_lml_grad_ard: null context");
-    if (!c->have_factor) return fail_arg("gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)");
+    if (!c->res.regression()) return fail_arg("gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)");
     if (c->kind != 0) return fail_arg("gpmi_lml_grad_ard: squared-exponential kernel only");
     HIP_TRY(hipSetDevice(c->device));
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
     const int64_t ld = c->ldA;
@@ -694,7 +673,7 @@ int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     std::vector<double> sums((size_t)nl * (size_t)(w + 3));
     HIP_TRY(hipMemcpyAsync(sums.data(), a.sums, sums.size() * 8, hipMemcpyDeviceToHost, s));
     int gave_up = 0;
-    if (c->factor_fused && tuning().trsv_vinv >= 2)
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
         HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
@@ -718,10 +697,9 @@ int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
 // the N^3/3 product -U U^T of the gradients is not needed.  Reads L, m and y only: every kernel kind.
 int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
     if (!c) return fail_arg("gpmi_loo: null context");
-    if (!c->have_factor) return fail_arg("gpmi_loo: no regression factorisation resident (call gpmi_factorize)");
+    if (!c->res.regression()) return fail_arg("gpmi_loo: no regression factorisation resident (call gpmi_factorize)");
     HIP_TRY(hipSetDevice(c->device));
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
     const int64_t N = c->N, Np = c->Np, ld = c->ldA;
@@ -742,7 +720,7 @@ int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
     double sum = 0.0;
     HIP_TRY(hipMemcpyAsync(&sum, dsum, 8, hipMemcpyDeviceToHost, s));
     int gave_up = 0;      // the one-launch backward solve's "a poll gave up" word, as gpmi_get_alpha reads it
-    if (c->factor_fused && tuning().trsv_vinv >= 2)
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
         HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
@@ -760,11 +738,10 @@ int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
 // never stored whole.  sigma and the noise need no N^3 product (dK_y = 2 (K_y - noise I) / sigma and I).
 int gpmi_loo_grad(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) {
     if (!c) return fail_arg("gpmi_loo_grad: null context");
-    if (!c->have_factor) return fail_arg("gpmi_loo_grad: no regression factorisation resident (call gpmi_factorize)");
+    if (!c->res.regression()) return fail_arg("gpmi_loo_grad: no regression factorisation resident (call gpmi_factorize)");
     if (c->kind != 0) return fail_arg("gpmi_loo_grad: squared-exponential kernel only");
     HIP_TRY(hipSetDevice(c->device));
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t s = c->stream;
     const int64_t N = c->N, Np = c->Np, ld = c->ldA;
@@ -803,7 +780,7 @@ int gpmi_loo_grad(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) 
     double h[3] = {0.0, 0.0, 0.0};
     HIP_TRY(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, s));
     int gave_up = 0;
-    if (c->factor_fused && tuning().trsv_vinv >= 2)
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
         HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
@@ -873,21 +850,21 @@ int gpmi_grad_trace(gpmi_ctx* c, const double* a_in, const double* b_in, int64_t
 // -- behind L when it rode through the augmented factorisation (gpmi_fit_predict_sample_resident), else formed now in P
 // (K_ss build, v^T v by one MFMA SYRK, the same Cholesky) unless P already holds it for this jitter
 static int post_factor_device(gpmi_ctx* c, double jitter, const double** factor, int64_t* ld, int64_t* bad_pivot) {
-    if (!c->have_v) return fail_arg("gpmi_post_chol: run gpmi_predict first");
+    if (!c->res.have_v) return fail_arg("gpmi_post_chol: run gpmi_predict first");
     hipStream_t s = c->stream;
     const int64_t np_ = c->np_, n = c->n;
     if (bad_pivot) *bad_pivot = 0;
-    if (c->post_in_A && c->v_in_A && jitter == c->post_jitter) {
+    if (c->res.post_rides(jitter)) {
         *factor = c->A.as<double>() + c->Np * c->ldA + c->Np;
         *ld = c->ldA;
         return GPMI_OK;
     }
-    if (c->post_in_P && jitter == c->post_jitter_P && c->post_gen_P == c->v_gen) {
+    if (c->res.post_cached(jitter)) {
         *factor = c->P.as<double>();
         *ld = c->ldP;
         return GPMI_OK;
     }
-    c->post_in_P = false;
+    c->res.drop_post_in_P();
     c->timers_reset({GPMI_T_POSTCHOL});
     c->ldP = np_ + 32;
     HIP_TRY(c->P.ensure((size_t)np_ * c->ldP * 8));
@@ -895,13 +872,8 @@ static int post_factor_device(gpmi_ctx* c, double jitter, const double** factor,
     const int64_t big = std::numeric_limits<int64_t>::max();
     HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, s));
     size_t sp = c->span_begin(GPMI_T_POSTCHOL);
-    RbfArgs r;   // K_ss + jitter*I, lower tiles (GP_regression.py:128,154)
-    r.A = r.B = c->x_test();
-    r.nA = r.nB = n; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = np_;
-    set_kernel_args(c, r);
-    r.diag_add = jitter; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->box_test(), c->box_test());
-    r.out = P; r.ld = c->ldP;
+    // K_ss + jitter*I, lower tiles (GP_regression.py:128,154)
+    const RbfArgs r = rbf_sym(c, c->x_test(), n, c->box_test(), jitter, np_, P, c->ldP);
     HIP_TRY(launch_rbf(s, r));
     GemmArgs g;  // P -= v^T v  (rows of V are the columns of v)
     g.C = P; g.A = g.B = c->v_rows();
@@ -919,9 +891,7 @@ static int post_factor_device(gpmi_ctx* c, double jitter, const double** factor,
         g_err = "Matrix is not positive definite";
         return GPMI_ERR_NOT_PD;
     }
-    c->post_in_P = true;
-    c->post_jitter_P = jitter;
-    c->post_gen_P = c->v_gen;
+    c->res.post_cached_in_P(jitter);
     *factor = P;
     *ld = c->ldP;
     return GPMI_OK;
@@ -985,15 +955,15 @@ static int lane_prepare(gpmi_ctx* c, gpmi_ctx* l) {
     HIP_TRY(hipMemcpyAsync(l->X.p, c->x_train(), (size_t)c->N * c->d * 8, hipMemcpyDeviceToDevice, l->stream));
     HIP_TRY(hipMemcpyAsync(l->y.p, c->y.p, (size_t)c->N * 8, hipMemcpyDeviceToDevice, l->stream));
     HIP_TRY(hipStreamSynchronize(l->stream));
-    l->have_train = true;
-    l->have_factor = l->have_v = l->have_test = false;
+    l->res.drop_train();
+    l->res.train_set();
     return GPMI_OK;
 }
 
 int gpmi_lml_batch(gpmi_ctx* c, const double* triples, int64_t T, double* lml_out, int* status_out) {
     if (!c || !triples || !lml_out) return fail_arg("gpmi_lml_batch: null argument");
     if (T < 0) return fail_arg("gpmi_lml_batch: T < 0");
-    if (!c->have_train) return fail_arg("gpmi_lml_batch: no training set (call gpmi_set_train)");
+    if (!c->res.have_train) return fail_arg("gpmi_lml_batch: no training set (call gpmi_set_train)");
     HIP_TRY(hipSetDevice(c->device));
     const int64_t Np = round_up(c->N, TILE);
     // lanes by size, measured with 24 triples per call (round 4, profiles/r04_lml_batch_lanes_small.txt; ms per triple with

@@ -12,6 +12,7 @@
 
 #include "../../include/gpmi.h"
 #include "gpmi_internal.h"
+#include "gpmi_state.h"
 
 namespace gpmi {
 
@@ -125,14 +126,7 @@ struct gpmi_ctx {
     gpmi::Tuning tune;      // kernel-selection options of this context (installed per call: gpmi::TuneScope)
     // training set / factor
     int64_t N = 0, d = 0, Np = 0, ldA = 0, Mp = 0;
-    bool have_train = false, have_factor = false;
-    // The resident factor's 128 x 128 diagonal blocks carry their full inverses (launch_vinv128; set by the first backward
-    // solve).  OWNERSHIP: from then on the strict block-upper 16 x 16 tiles of every diagonal block of A hold L_kk^-T, not
-    // zeros and not K: nothing but the backward-solve kernels may read them (every other consumer of a diagonal block masks
-    // to the lower triangle; gpmi_get_factor_block zeroes the upper triangle on the way out).
-    bool have_vinv = false;
-    int factor_fused = 1;    // the resident factor came from the fused panel kernels: its diagonal 16 x 16 tiles carry
-                             // their inverses above the diagonal, which trsm128 reads (panel_mfma.hip)
+    gpmi::Resident res;      // what is resident and what was derived from it: gpmi_state.h, the only place that changes it
     double sig2 = 1.0, coef = -0.5;
     int kind = 0;            // covariance function: 0 rbf, 1 linear, 2 periodic, 3 CO2 composite (gpmi_set_kernel*)
     double kp0 = 0., kp1 = 0.;
@@ -140,19 +134,12 @@ struct gpmi_ctx {
     DevBuf X, y, A, info, red;
     // test set
     int64_t n = 0, np_ = 0, ldV = 0, ldP = 0;
-    bool have_test = false, have_v = false;
-    bool v_in_A = false;     // v^T is resident in rows of A (gpmi_fit_predict_resident: from row v_row0), not in V
-    int64_t v_row0 = 0;
-    double* v_rows() { return v_in_A ? A.as<double>() + v_row0 * ldA : V.as<double>(); }
+    int64_t v_row0 = 0;      // v^T in rows of A (gpmi_fit_predict_resident, res.v_in_A) starts at this row
+    double* v_rows() { return res.v_in_A ? A.as<double>() + v_row0 * ldA : V.as<double>(); }
     // the y rows: row Np of A -- or, when the posterior factor rides as well (gpmi_fit_predict_sample_resident), behind the
     // test rows, whose own n_p columns then follow the training columns
     int64_t yrow = 0;
     double* m_row() { return A.as<double>() + yrow * ldA; }
-    bool post_in_A = false;  // A[Np.., Np..] holds cholesky(K_ss + post_jitter I - v^T v) of the resident test set
-    double post_jitter = 0.0;
-    bool post_in_P = false;  // ... or P does (gpmi_post_chol / gpmi_post_sample on a resident v), for post_jitter_P and the
-    double post_jitter_P = 0.0;   // v of generation post_gen_P (v_gen counts every (re)computation of v)
-    uint64_t v_gen = 0, post_gen_P = 0;
     std::vector<double> hXs; // host copy of the test inputs (diag(K_ss) of the linear kernel)
     Box boxX, boxXs;         // bounding boxes of the training / test inputs
     // Per-dimension relative lengthscales r_k (gpmi_set_lengthscales; empty: isotropic).  X and Xs keep the raw inputs;
@@ -170,7 +157,6 @@ struct gpmi_ctx {
     DevBuf Xs, V, P, vec, dense;
     DevBuf flag;             // one int the single-launch backward solve sets if a poll gave up
     DevBuf vside;            // Np x 128: the inverses of the 128 x 128 diagonal blocks, row-major (launch_vinv128's side buffer)
-    bool have_vside = false; // vside matches the resident factor
     DevBuf cov_a, cov_b, cov_out;   // gpmi_rbf / gpmi_cov staging, kept across calls (the BO loops call them hundreds of times)
     DevBuf U, Kn, gpart;     // f2: L^-T, -(K+sI)^-1, per-tile partial sums of the gradient trace
     DevBuf gsum;             // gpmi_lml_grad_ard: the d + 3 sums, reduced on the device
@@ -179,23 +165,16 @@ struct gpmi_ctx {
     DevBuf loov, loow;       // gpmi_loo / gpmi_loo_grad: the per-point vectors; the NB x ld row block of K_y^-1 D
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
-    // A Laplace factor is not a regression factor: gpmi_laplace_fit clears have_factor, every regression factorisation
-    // (and anything else that clears have_factor) clears have_laplace.
-    bool have_laplace = false;
     DevBuf lap, lap_part, lap_out;
     // multi-class classification (softmax.hip): A holds M = chol(sum_c E_c) at the mode, sm_E the C matrices -E_c (full,
-    // symmetric), sm the C x Np vectors (Y - P among them).  The rule above extended by one flag: a softmax fit clears
-    // have_factor and have_laplace, a regression or binary fit clears have_softmax.  K and V = S_c L_c^-T are scratch of
-    // the fit and live in Kn and U (the scratch of gpmi_lml_grad).
-    bool have_softmax = false;
+    // symmetric), sm the C x Np vectors (Y - P among them).  K and V = S_c L_c^-T are scratch of the fit and live in Kn
+    // and U (the scratch of gpmi_lml_grad).
     int sm_classes = 0;
     DevBuf sm, sm_part, sm_E, sm_B, sm_out;
     // sparse regression with inducing points (sparse.hip): sp_L holds L = chol(K_uu + jitter I) (sp_mp x sp_ld), sp_B the
     // factor L_B of B = I + A~ A~^T with c = L_B^-1 A~ y~ in its row sp_mp, sp_Z the (scaled) inducing inputs, sp_q the N
-    // values q_i, sp_W the slab workspace (sp_wrows x sp_ld) that prediction reuses for its chunks of test rows.  A and
-    // the regression state are not touched, but the rule above holds with one more flag: a sparse fit clears have_factor,
-    // have_laplace and have_softmax, and whatever clears have_factor clears have_sparse.
-    bool have_sparse = false;
+    // values q_i, sp_W the slab workspace (sp_wrows x sp_ld) that prediction reuses for its chunks of test rows.  A is
+    // not touched.
     int sp_method = 0, sp_fused = 1;
     int64_t sparse_slab = 0;     // option "sparse_slab": training rows per slab (0 = by size), rounded up to 128
     int64_t sp_m = 0, sp_mp = 0, sp_ld = 0, sp_wrows = 0;
@@ -273,7 +252,15 @@ hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri 
 // the same sweep through any resident lower factor (ncols x ncols, leading dimension ld), not only the one in c->A
 hipError_t solve_sweep_factor(gpmi_ctx* c, const double* L, int64_t ld, int64_t ncols, double* V, int64_t ldv, int64_t m,
                               bool tri = false);
-void set_kernel_args(const gpmi_ctx* c, RbfArgs& r);
+// The kernel-matrix launches of a context, ready for launch_rbf.  rbf_cross: rows row0 .. row0 + nrows of K(A, B) for point
+// sets of nA and nB points with boxes ba and bb, ncols columns, nothing on the diagonal; the delta term of the composite
+// kernel counts as on a square matrix only for the test set against a training set of the same size.  rbf_sym: the lower
+// tiles of K(X, X) + diag_add I, npad x npad.
+RbfArgs rbf_cross(const gpmi_ctx* c, const double* A, int64_t nA, const Box& ba, const double* B, int64_t nB, const Box& bb,
+                  int64_t row0, int64_t nrows, int64_t ncols, double* out, int64_t ld);
+RbfArgs rbf_sym(const gpmi_ctx* c, const double* X, int64_t n, const Box& box, double diag_add, int64_t npad, double* out,
+                int64_t ld);
+RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld);      // K(X*, X), n_p x Np
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows = 0, bool test_cols = false);
 // with_test: the test set's rows K(X*, X) ride below the y rows (they come out as v^T = K_s^T L^-T, a7 inside a3) and
 // mean / variance (a6, a8) are read off them behind the LML
@@ -288,11 +275,35 @@ int ard_rescale_test(gpmi_ctx* c);
 void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, double* out2, int want_sd);
 // gpmi_api.hip: L^T x = b on the resident fused factor (a5; the first call after a factorisation inverts its diagonal blocks)
 hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout);
+// x = L^-T m for the m of the y row, through the fused solve or the plain one as the resident factor asks: x2 holds 2 Np
+// doubles, *x_out says where in it the solution lies
+hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out);
+// the context's options with the panel kind of the resident factor: solve with the kind of leaves that produced it
+inline Tuning resident_tuning(const gpmi_ctx* c) {
+    Tuning tn = c->tune;
+    tn.panel_fused = c->res.factor_fused;
+    return tn;
+}
 
 // laplace.hip: GPML Algorithms 3.1 (Newton iteration for the mode, logistic likelihood) and 3.2 (prediction)
 int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat);
 int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob);
+// The Newton skeleton of both classifiers (laplace.hip).  classifier_fit_check: the arguments both take, under the
+// caller's API name; `own` is the text of a failed check of the caller's own arguments (or null), reported at its place
+// behind the kernel check.  classifier_fit_begin: the resident fit goes, A and the hyper-parameters are set up, the
+// backward solve's give-up word (*chain: it is read from the first iteration on) and the pivot word are reset.
+// newton_readback, behind the caller's per-point kernel: Psi from its partials with the pivot and give-up words in one
+// record, h = {Psi, pivot word, give-up word}, the iteration's one synchronisation, and the record's status under the
+// caller's API name and its text for a bad pivot.
+constexpr int64_t NO_BAD_PIVOT = std::numeric_limits<int64_t>::max();
+int classifier_fit_check(const gpmi_ctx* c, const char* api, const char* own, double sigma, double ell, double tol,
+                         int max_iter);
+int classifier_fit_begin(gpmi_ctx* c, double sigma, double ell, bool* chain);
+hipError_t launch_newton_psi(hipStream_t st, const double* psi_part, int64_t nblk, const int64_t* info, const int* flag,
+                             double* out);
+int newton_readback(gpmi_ctx* c, const double* psi_part, int64_t nblk, bool chain, double* rec, double (&h)[3],
+                    const char* api, const char* pivot_text);
 void laplace_quad_nodes(double sig2, int* M, double* T, double* h);
 
 // softmax.hip: GPML Algorithms 3.3 (Newton iteration for the mode, softmax likelihood, C latent functions with one shared

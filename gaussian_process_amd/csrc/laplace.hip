@@ -6,8 +6,9 @@
 //   laplace_symv_kernel<false>  f = K a over the lower tiles of the freshly built K (one read of the lower triangle)
 //   laplace_symv_kernel<true>   u = K b and, in the same pass, K <- B on the lower tiles (one read, one write)
 //   laplace_newton_kernel       f from the tile partials (or the halved step), pi, W^1/2, grad, b and the partials of Psi
-//   laplace_psi_kernel          Psi = -a^T f / 2 + sum log p(y|f) in a fixed order, with the Cholesky's pivot word and the
-//                               backward solve's give-up word, so an iteration reads back one small record
+//   newton_psi_kernel           Psi = -a^T f / 2 + sum log p(y|f) in a fixed order, with the Cholesky's pivot word and the
+//                               backward solve's give-up word, so an iteration reads back one small record (softmax.hip
+//                               uses it too, with the rest of the Newton skeleton at the end of this file's kernels)
 //   laplace_rhs_kernel          c = W^1/2 (K b) from the tile partials
 //   laplace_update_kernel       a <- b - W^1/2 x (keeping the previous a, f for step halving)
 //   laplace_rows_kernel         prediction: f* = K(X*, X) grad, then the rows are scaled by W^1/2 in place
@@ -185,9 +186,9 @@ __global__ __launch_bounds__(VEC_THREADS) void laplace_newton_kernel(int mode, c
 
 // out[0] = Psi = -a^T f / 2 + sum log p, out[1] = the Cholesky's first bad pivot (INT64_MAX: none) as a double,
 // out[2] = the backward solve's give-up word (0 without one)
-__global__ __launch_bounds__(VEC_THREADS) void laplace_psi_kernel(const double* __restrict__ psi_part, int64_t nblk,
-                                                                  const int64_t* __restrict__ info,
-                                                                  const int* __restrict__ flag, double* __restrict__ out) {
+__global__ __launch_bounds__(VEC_THREADS) void newton_psi_kernel(const double* __restrict__ psi_part, int64_t nblk,
+                                                                 const int64_t* __restrict__ info,
+                                                                 const int* __restrict__ flag, double* __restrict__ out) {
     __shared__ double sh[2 * (VEC_THREADS / 64)];
     double af = 0.0, lp = 0.0;
     for (int64_t k = threadIdx.x; k < nblk; k += VEC_THREADS) { af += psi_part[2 * k]; lp += psi_part[2 * k + 1]; }
@@ -264,6 +265,55 @@ unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THRE
 
 }  // namespace
 
+hipError_t launch_newton_psi(hipStream_t st, const double* psi_part, int64_t nblk, const int64_t* info, const int* flag,
+                             double* out) {
+    hipLaunchKernelGGL(newton_psi_kernel, dim3(1), dim3(VEC_THREADS), 0, st, psi_part, nblk, info, flag, out);
+    return hipGetLastError();
+}
+
+int newton_readback(gpmi_ctx* c, const double* psi_part, int64_t nblk, bool chain, double* rec, double (&h)[3],
+                    const char* api, const char* pivot_text) {
+    hipStream_t st = c->stream;
+    HIP_TRY(launch_newton_psi(st, psi_part, nblk, c->info.as<int64_t>(), chain ? c->flag.as<int>() : nullptr, rec));
+    HIP_TRY(hipMemcpyAsync(h, rec, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+    const std::string who = std::string(api) + ": ";
+    if (h[1] != (double)NO_BAD_PIVOT) { g_err = who + pivot_text; return GPMI_ERR_NOT_PD; }
+    if (h[2] != 0.0) return fail_runtime(hipErrorUnknown, (who + "the single-launch backward solve gave up waiting for a block").c_str());
+    if (!std::isfinite(h[0])) return fail_arg((who + "the objective is not finite").c_str());
+    return GPMI_OK;
+}
+
+int classifier_fit_check(const gpmi_ctx* c, const char* api, const char* own, double sigma, double ell, double tol,
+                         int max_iter) {
+    const std::string who = std::string(api) + ": ";
+    if (!c->res.have_train) return fail_arg((who + "no training set (call gpmi_set_train)").c_str());
+    if (c->kind != 0) return fail_arg((who + "squared-exponential kernel only (gpmi_set_kernel kind 0)").c_str());
+    if (own) return fail_arg((who + own).c_str());
+    if (!(ell != 0.0) || !std::isfinite(ell) || !std::isfinite(sigma))
+        return fail_arg((who + "ell must be non-zero and hyper-parameters finite").c_str());
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail_arg((who + "tol must be finite and >= 0").c_str());
+    if (max_iter < 0) return fail_arg((who + "max_iter must be >= 0").c_str());
+    return GPMI_OK;
+}
+
+int classifier_fit_begin(gpmi_ctx* c, double sigma, double ell, bool* chain) {
+    c->res.drop_fit();                    // a classifier's factor replaces whatever was resident: no other state survives
+    int rc = ensure_train_buffers(c, 0, false);
+    if (rc) return rc;
+    c->sig2 = sigma * sigma;
+    c->coef = -.5 * (1 / (ell * ell));
+    c->sigma = sigma; c->ell = ell;
+    *chain = tuning().panel_fused && tuning().trsv_vinv >= 2;
+    if (*chain) {                         // the give-up word is read from the first iteration on
+        HIP_TRY(c->flag.ensure(64));
+        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 64, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c->info.p, &NO_BAD_PIVOT, sizeof NO_BAD_PIVOT, hipMemcpyHostToDevice, c->stream));
+    return GPMI_OK;
+}
+
 // The node count of the prediction's quadrature (mirrored in tests/laplace_ref.py).  The integrand
 // expit(mu + sqrt(V) t) phi(t) is analytic in the strip |Im t| < pi / sqrt(V); with a = 0.9 pi / sqrt(V) the composite
 // trapezoid rule's error is about 2 M(a) exp(a^2 / 2 - 2 pi a / h) (M(a) < 4: |expit| on the strip's edge), so
@@ -306,14 +356,12 @@ static hipError_t launch_symv(gpmi_ctx* c, bool scale, const double* x) {
     return hipGetLastError();
 }
 
+static const char* const PIVOT_TEXT = "B = I + W^1/2 K W^1/2 met a non-positive pivot";
+
 int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat) {
-    if (!c->have_train) return fail_arg("gpmi_laplace_fit: no training set (call gpmi_set_train)");
-    if (c->kind != 0) return fail_arg("gpmi_laplace_fit: squared-exponential kernel only (gpmi_set_kernel kind 0)");
-    if (!(ell != 0.0) || !std::isfinite(ell) || !std::isfinite(sigma))
-        return fail_arg("gpmi_laplace_fit: ell must be non-zero and hyper-parameters finite");
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail_arg("gpmi_laplace_fit: tol must be finite and >= 0");
-    if (max_iter < 0) return fail_arg("gpmi_laplace_fit: max_iter must be >= 0");
+    int rc = classifier_fit_check(c, "gpmi_laplace_fit", nullptr, sigma, ell, tol, max_iter);
+    if (rc) return rc;
     hipStream_t st = c->stream;
     const int64_t N = c->N;
     {
@@ -323,21 +371,8 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
         for (double v : hy)
             if (v != 1.0 && v != -1.0) return fail_arg("gpmi_laplace_fit: labels must be exactly -1 or +1");
     }
-    int rc = ensure_train_buffers(c, 0, false);
-    if (rc) return rc;
-    // the Laplace factor replaces whatever was resident: no regression state survives
-    c->have_factor = false;
-    c->have_laplace = false;
-    c->have_softmax = false;
-    c->have_sparse = false;
-    c->v_in_A = false;
-    c->have_vinv = false;
-    c->have_vside = false;
-    c->have_v = false;
-    c->post_in_P = false;
-    c->sig2 = sigma * sigma;
-    c->coef = -.5 * (1 / (ell * ell));
-    c->sigma = sigma; c->ell = ell;
+    bool chain = false;
+    if ((rc = classifier_fit_begin(c, sigma, ell, &chain)) != GPMI_OK) return rc;
     const int64_t Np = c->Np, nt = Np / TILE;
     const int64_t nblk = (Np + VEC_THREADS - 1) / VEC_THREADS;
     HIP_TRY(c->lap.ensure(((size_t)LV_COUNT * Np + 2 * nblk + 8) * 8));
@@ -347,23 +382,9 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     double* rec = psi_part + 2 * nblk;
     const NewtonVecs v = newton_vecs(c);
     double* A = c->A.as<double>();
-    const bool chain = tuning().panel_fused && tuning().trsv_vinv >= 2;
-    if (chain) {                          // the give-up word is read from the first iteration on
-        HIP_TRY(c->flag.ensure(64));
-        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 64, st));
-    }
     HIP_TRY(hipMemsetAsync(v.a, 0, (size_t)Np * 8, st));
     HIP_TRY(launch_fill_rows(st, c->m_row(), c->ldA, TILE, Np, 0.0));
-    const int64_t big = std::numeric_limits<int64_t>::max();
-    HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, st));
-
-    RbfArgs r;
-    r.A = r.B = c->x_train();
-    r.nA = r.nB = N; r.d = c->d; r.row0 = 0; r.nrows = Np; r.ncols = Np;
-    set_kernel_args(c, r);
-    r.diag_add = 0.0; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->box_train(), c->box_train());
-    r.out = A; r.ld = c->ldA;
+    const RbfArgs r = rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, A, c->ldA);
 
     // Psi of the current iterate, with the previous Cholesky's pivot word and backward solve's give-up word
     double h[3];
@@ -371,16 +392,7 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
         hipLaunchKernelGGL(laplace_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, st, mode,
                            (const double*)c->lap_part.as<double>(), nt, N, Np, (const double*)c->y.as<double>(), v, psi_part);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(laplace_psi_kernel, dim3(1), dim3(VEC_THREADS), 0, st, (const double*)psi_part, nblk,
-                           (const int64_t*)c->info.as<int64_t>(), (const int*)(chain ? c->flag.as<int>() : nullptr), rec);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, rec, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        c->timers_collect();
-        if (h[1] != (double)big) { g_err = "gpmi_laplace_fit: B = I + W^1/2 K W^1/2 met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
-        if (h[2] != 0.0) return fail_runtime(hipErrorUnknown, "gpmi_laplace_fit: the single-launch backward solve gave up waiting for a block");
-        if (!std::isfinite(h[0])) return fail_arg("gpmi_laplace_fit: the objective is not finite");
-        return GPMI_OK;
+        return newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_laplace_fit", PIVOT_TEXT);
     };
 
     double psi_prev = 0.0;
@@ -391,15 +403,10 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
         HIP_TRY(launch_symv(c, false, v.a));                          // 2. f = K a
         if ((rc = evaluate(0)) != GPMI_OK) return rc;                 // 3.
         if (have_prev) {                                              // 4.
-            for (int halvings = 0;;) {
-                const double d = h[0] - psi_prev, thr = tol * std::max(1.0, std::fabs(h[0]));
-                if (std::fabs(d) <= thr) { conv = true; break; }
-                if (d < -thr && halvings < 20) {
-                    if ((rc = evaluate(1)) != GPMI_OK) return rc;
-                    ++halvings;
-                    continue;
-                }
-                break;
+            for (int halvings = 0;; ++halvings) {
+                const Step step = newton_decide(h[0], psi_prev, tol, halvings);
+                if (step != Step::Halve) { conv = step == Step::Converged; break; }
+                if ((rc = evaluate(1)) != GPMI_OK) return rc;
             }
         }
         HIP_TRY(launch_symv(c, true, v.b));                           // 5. u = K b, K <- B
@@ -408,17 +415,10 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
         HIP_TRY(hipGetLastError());
         HIP_TRY(launch_set_yrow(st, c->m_row(), L + LV_C * Np, N, Np));   // 6. c rides: m = L^-1 c
         HIP_TRY(cholesky_inplace(c, A, c->ldA, Np, c->Mp, c->info.as<int64_t>(), false));
-        c->have_vinv = c->have_vside = false;
-        c->factor_fused = tuning().panel_fused;
+        c->res.factor_replaced(tuning().panel_fused);
         if (conv || it >= max_iter) break;
-        double* x = L + LV_X * Np;                                    // 7. x = L^-T m, a = b - s o x
-        HIP_TRY(hipMemcpyAsync(x, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, st));
-        if (c->factor_fused) {
-            HIP_TRY(backward_solve_fused(c, x, x + Np));
-            x += Np;
-        } else {
-            HIP_TRY(launch_trsv_lt(st, A, c->ldA, x, Np));
-        }
+        double* x = nullptr;                                          // 7. x = L^-T m, a = b - s o x
+        HIP_TRY(backward_solve_resident(c, L + LV_X * Np, &x));
         hipLaunchKernelGGL(laplace_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, (const double*)x, v);
         HIP_TRY(hipGetLastError());
         psi_prev = h[0];
@@ -434,24 +434,22 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     if (f_hat) HIP_TRY(hipMemcpyAsync(f_hat, v.f, (size_t)N * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
-    if (info != big) { g_err = "gpmi_laplace_fit: B = I + W^1/2 K W^1/2 met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
+    if (info != NO_BAD_PIVOT) { g_err = std::string("gpmi_laplace_fit: ") + PIVOT_TEXT; return GPMI_ERR_NOT_PD; }
     if (log_q) *log_q = h[0] - red[0];
     if (iters) *iters = it;
     if (converged) *converged = conv ? 1 : 0;
-    c->have_laplace = true;
+    c->res.fit_done(Fit::Laplace);
     return GPMI_OK;
 }
 
 int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob) {
-    if (!c->have_laplace) return fail_arg("gpmi_laplace_predict: no Laplace fit resident (call gpmi_laplace_fit)");
-    if (!c->have_test) return fail_arg("gpmi_laplace_predict: no test set (call gpmi_set_test)");
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;      // solve with the kind of leaves that produced the resident factor
+    if (!c->res.laplace()) return fail_arg("gpmi_laplace_predict: no Laplace fit resident (call gpmi_laplace_fit)");
+    if (!c->res.have_test) return fail_arg("gpmi_laplace_predict: no test set (call gpmi_set_test)");
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t st = c->stream;
     const int64_t Np = c->Np, np_ = c->np_, n = c->n;
-    c->have_v = false;
-    c->v_in_A = false;
+    c->res.drop_v();
     c->ldV = Np + c->ld_pad;
     HIP_TRY(c->V.ensure((size_t)np_ * c->ldV * 8));
     HIP_TRY(c->lap_out.ensure((size_t)np_ * 5 * 8));
@@ -460,14 +458,7 @@ int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* pro
     const double* grad = c->lap.as<double>() + LV_G * Np;
     const double* s = c->lap.as<double>() + LV_S * Np;
 
-    RbfArgs r;                            // R = K(X*, X)
-    r.A = c->x_test(); r.B = c->x_train();
-    r.nA = n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = Np;
-    set_kernel_args(c, r);
-    r.diag_add = 0.; r.symmetric = 0;
-    r.delta_square = (n == c->N) ? 1 : 0;
-    r.max_sq = box_max_sq(c->box_test(), c->box_train());
-    r.out = V; r.ld = c->ldV;
+    const RbfArgs r = rbf_test_train(c, V, c->ldV);       // R = K(X*, X)
     HIP_TRY(launch_rbf(st, r));
     hipLaunchKernelGGL(laplace_rows_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, V, c->ldV, Np, grad, s, o);
     HIP_TRY(hipGetLastError());

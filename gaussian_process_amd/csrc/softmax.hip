@@ -11,7 +11,7 @@
 //   softmax_bmat_kernel      A <- I + s_c s_c^T o K on the lower tiles, from the kept K
 //   softmax_newton_kernel    per point: F from the tile partials (or the halved step), P, sqrt(P), Y - P,
 //                            B = P o F - P o sum_c(P o F) + Y - P and the partials of Psi (max-subtracted logsumexp)
-//   softmax_psi_kernel       Psi in a fixed order with the Cholesky's pivot word and the backward solve's give-up word
+//   (newton_psi_kernel of laplace.hip: Psi in a fixed order with the Cholesky's pivot word and the solve's give-up word)
 //   softmax_vec_kernel       C vectors from the tile partials (K b_c; c_c = E_c K b_c and sum_c c_c)
 //   softmax_esum_kernel      A <- sum_c E_c on the lower tiles (identity on the padding)
 //   softmax_update_kernel    A <- B - C + [E_c t]_c (keeping the previous A, F for step halving)
@@ -277,22 +277,6 @@ __global__ __launch_bounds__(VEC_THREADS) void softmax_newton_kernel(int mode, c
     if (threadIdx.x == 0) { psi_part[2 * blockIdx.x] = af; psi_part[2 * blockIdx.x + 1] = lp; }
 }
 
-// out[0] = Psi = -sum(A o F) / 2 + sum log p, out[1] = the Cholesky's first bad pivot (INT64_MAX: none) as a double,
-// out[2] = the backward solve's give-up word (0 without one)
-__global__ __launch_bounds__(VEC_THREADS) void softmax_psi_kernel(const double* __restrict__ psi_part, int64_t nblk,
-                                                                  const int64_t* __restrict__ info,
-                                                                  const int* __restrict__ flag, double* __restrict__ out) {
-    __shared__ double sh[2 * (VEC_THREADS / 64)];
-    double af = 0.0, lp = 0.0;
-    for (int64_t k = threadIdx.x; k < nblk; k += VEC_THREADS) { af += psi_part[2 * k]; lp += psi_part[2 * k + 1]; }
-    wg_reduce2(af, lp, sh);
-    if (threadIdx.x == 0) {
-        out[0] = -0.5 * af + lp;
-        out[1] = (double)*info;
-        out[2] = flag ? (double)*flag : 0.0;
-    }
-}
-
 // out_c[i] = sign * (tile partials of vector c summed), 0 past N; total (optional) = sum_c out_c[i] in index order
 __global__ __launch_bounds__(VEC_THREADS) void softmax_vec_kernel(const double* __restrict__ part, int64_t nt, int64_t N,
                                                                   int64_t Np, int C, double sign, double* __restrict__ out,
@@ -469,15 +453,14 @@ enum { SW_CSUM, SW_X, SW_VECS = SW_X + 2 };
 
 }  // namespace
 
+static const char* const PIVOT_TEXT = "a Cholesky factorisation met a non-positive pivot";
+
 int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat) {
-    if (!c->have_train) return fail_arg("gpmi_softmax_fit: no training set (call gpmi_set_train)");
-    if (c->kind != 0) return fail_arg("gpmi_softmax_fit: squared-exponential kernel only (gpmi_set_kernel kind 0)");
-    if (C < 2 || C > MAXC) return fail_arg("gpmi_softmax_fit: n_classes must lie in [2, GPMI_SOFTMAX_MAX_CLASSES]");
-    if (!(ell != 0.0) || !std::isfinite(ell) || !std::isfinite(sigma))
-        return fail_arg("gpmi_softmax_fit: ell must be non-zero and hyper-parameters finite");
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail_arg("gpmi_softmax_fit: tol must be finite and >= 0");
-    if (max_iter < 0) return fail_arg("gpmi_softmax_fit: max_iter must be >= 0");
+    int rc = classifier_fit_check(c, "gpmi_softmax_fit",
+                                  C < 2 || C > MAXC ? "n_classes must lie in [2, GPMI_SOFTMAX_MAX_CLASSES]" : nullptr, sigma,
+                                  ell, tol, max_iter);
+    if (rc) return rc;
     hipStream_t st = c->stream;
     const int64_t N = c->N;
     {
@@ -488,21 +471,8 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
             if (!(v >= 0.0 && v < (double)C && v == std::floor(v)))
                 return fail_arg("gpmi_softmax_fit: labels must be integers in [0, n_classes)");
     }
-    // the softmax state replaces whatever was resident: no regression factor and no binary Laplace fit survives
-    c->have_factor = false;
-    c->have_laplace = false;
-    c->have_softmax = false;
-    c->have_sparse = false;
-    c->v_in_A = false;
-    c->have_vinv = false;
-    c->have_vside = false;
-    c->have_v = false;
-    c->post_in_P = false;
-    int rc = ensure_train_buffers(c, 0, false);
-    if (rc) return rc;
-    c->sig2 = sigma * sigma;
-    c->coef = -.5 * (1 / (ell * ell));
-    c->sigma = sigma; c->ell = ell;
+    bool chain = false;
+    if ((rc = classifier_fit_begin(c, sigma, ell, &chain)) != GPMI_OK) return rc;
     const int64_t Np = c->Np, nt = Np / TILE, ld = c->ldA;
     const int64_t nblk = (Np + VEC_THREADS - 1) / VEC_THREADS;
     const int64_t msize = Np * ld;                  // doubles of one N x N matrix
@@ -524,22 +494,8 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     double* nE = c->sm_E.as<double>();
     double* part = c->sm_part.as<double>();
     const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
-    const bool chain = tuning().panel_fused && tuning().trsv_vinv >= 2;
-    if (chain) {                          // the give-up word is read from the first iteration on
-        HIP_TRY(c->flag.ensure(64));
-        HIP_TRY(hipMemsetAsync(c->flag.p, 0, 64, st));
-    }
     HIP_TRY(hipMemsetAsync(v.a, 0, (size_t)C * Np * 8, st));
-    const int64_t big = std::numeric_limits<int64_t>::max();
-    HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, st));
-
-    RbfArgs r;                            // K, once per fit
-    r.A = r.B = c->x_train();
-    r.nA = r.nB = N; r.d = c->d; r.row0 = 0; r.nrows = Np; r.ncols = Np;
-    set_kernel_args(c, r);
-    r.diag_add = 0.0; r.symmetric = 1; r.delta_square = 1;
-    r.max_sq = box_max_sq(c->box_train(), c->box_train());
-    r.out = K; r.ld = ld;
+    const RbfArgs r = rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, K, ld);    // K, once per fit
     HIP_TRY(launch_rbf(st, r));
 
     SymvArgs kx;                          // K times C vectors
@@ -552,16 +508,7 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
         hipLaunchKernelGGL(softmax_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, st, mode, (const double*)part,
                            nt, N, Np, C, (const double*)c->y.as<double>(), v, psi_part);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(softmax_psi_kernel, dim3(1), dim3(VEC_THREADS), 0, st, (const double*)psi_part, nblk,
-                           (const int64_t*)c->info.as<int64_t>(), (const int*)(chain ? c->flag.as<int>() : nullptr), rec);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h, rec, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        c->timers_collect();
-        if (h[1] != (double)big) { g_err = "gpmi_softmax_fit: a Cholesky factorisation met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
-        if (h[2] != 0.0) return fail_runtime(hipErrorUnknown, "gpmi_softmax_fit: the single-launch backward solve gave up waiting for a block");
-        if (!std::isfinite(h[0])) return fail_arg("gpmi_softmax_fit: the objective is not finite");
-        return GPMI_OK;
+        return newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_softmax_fit", PIVOT_TEXT);
     };
 
     double psi_prev = 0.0;
@@ -572,15 +519,10 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
         HIP_TRY(launch_symv(st, kx, 1));
         if ((rc = evaluate(0)) != GPMI_OK) return rc;
         if (have_prev) {                                              // 2.
-            for (int halvings = 0;;) {
-                const double d = h[0] - psi_prev, thr = tol * std::max(1.0, std::fabs(h[0]));
-                if (std::fabs(d) <= thr) { conv = true; break; }
-                if (d < -thr && halvings < 20) {
-                    if ((rc = evaluate(1)) != GPMI_OK) return rc;
-                    ++halvings;
-                    continue;
-                }
-                break;
+            for (int halvings = 0;; ++halvings) {
+                const Step step = newton_decide(h[0], psi_prev, tol, halvings);
+                if (step != Step::Halve) { conv = step == Step::Converged; break; }
+                if ((rc = evaluate(1)) != GPMI_OK) return rc;
             }
         }
         const bool last = conv || it >= max_iter;
@@ -591,8 +533,7 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
             hipLaunchKernelGGL(softmax_bmat_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)K, A, ld, N, sk);
             HIP_TRY(hipGetLastError());
             HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
-            c->have_vinv = c->have_vside = false;
-            c->factor_fused = tuning().panel_fused;
+            c->res.factor_replaced(tuning().panel_fused);
             HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * k));
             HIP_TRY(launch_fill_rows(st, V, ld, Np, Np, 0.0));
             hipLaunchKernelGGL(softmax_seed_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, V, ld, Np, sk);
@@ -628,18 +569,11 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
         hipLaunchKernelGGL(softmax_esum_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)nE, msize, C, A, ld, N);
         HIP_TRY(hipGetLastError());
         HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
-        c->have_vinv = c->have_vside = false;
-        c->factor_fused = tuning().panel_fused;
+        c->res.factor_replaced(tuning().panel_fused);
         HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * C));
         if (last) break;
-        double* x = wv + SW_X * Np;                                   // 6. t = M^-T M^-1 sum_c c_c, A <- B - C + [E_c t]
-        HIP_TRY(hipMemcpyAsync(x, c->m_row(), (size_t)Np * 8, hipMemcpyDeviceToDevice, st));
-        if (c->factor_fused) {
-            HIP_TRY(backward_solve_fused(c, x, x + Np));
-            x += Np;
-        } else {
-            HIP_TRY(launch_trsv_lt(st, A, ld, x, Np));
-        }
+        double* x = nullptr;                                          // 6. t = M^-T M^-1 sum_c c_c, A <- B - C + [E_c t]
+        HIP_TRY(backward_solve_resident(c, wv + SW_X * Np, &x));
         ex.x = x; ex.xstride = 0;
         HIP_TRY(launch_symv(st, ex, C));
         hipLaunchKernelGGL(softmax_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np,
@@ -664,7 +598,7 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
         HIP_TRY(hipMemcpy2DAsync(f_hat, (size_t)N * 8, v.f, (size_t)Np * 8, (size_t)N * 8, (size_t)C, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
-    if (info != big) { g_err = "gpmi_softmax_fit: a Cholesky factorisation met a non-positive pivot"; return GPMI_ERR_NOT_PD; }
+    if (info != NO_BAD_PIVOT) { g_err = std::string("gpmi_softmax_fit: ") + PIVOT_TEXT; return GPMI_ERR_NOT_PD; }
     // log q = Psi - sum_c sum log diag L_c - sum log diag M
     double z = 0.0;
     for (int k = 0; k < C; ++k) z += red[2 * (size_t)k];
@@ -672,22 +606,20 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     if (iters) *iters = it;
     if (converged) *converged = conv ? 1 : 0;
     c->sm_classes = C;
-    c->have_softmax = true;
+    c->res.fit_done(Fit::Softmax);
     return GPMI_OK;
 }
 
 int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const double* normals, double* prob) {
-    if (!c->have_softmax) return fail_arg("gpmi_softmax_predict: no softmax fit resident (call gpmi_softmax_fit)");
-    if (!c->have_test) return fail_arg("gpmi_softmax_predict: no test set (call gpmi_set_test)");
+    if (!c->res.softmax()) return fail_arg("gpmi_softmax_predict: no softmax fit resident (call gpmi_softmax_fit)");
+    if (!c->res.have_test) return fail_arg("gpmi_softmax_predict: no test set (call gpmi_set_test)");
     if (S < 0 || (S > 0 && (!normals || !prob))) return fail_arg("gpmi_softmax_predict: n_samples > 0 needs normals and prob");
-    Tuning tn = c->tune;
-    tn.panel_fused = c->factor_fused;      // solve with the kind of leaves that produced the resident factor
+    const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     hipStream_t st = c->stream;
     const int C = c->sm_classes;
     const int64_t Np = c->Np, np_ = c->np_, n = c->n, ld = c->ldA, msize = Np * ld;
-    c->have_v = false;
-    c->v_in_A = false;
+    c->res.drop_v();
     c->ldV = Np + c->ld_pad;
     const int64_t ldV = c->ldV;
     HIP_TRY(c->V.ensure((size_t)np_ * ldV * 8));
@@ -703,14 +635,7 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     const double* G = c->sm.as<double>() + (int64_t)SV_G * C * Np;
     const double* nE = c->sm_E.as<double>();
 
-    RbfArgs r;                            // R = K(X*, X)
-    r.A = c->x_test(); r.B = c->x_train();
-    r.nA = n; r.nB = c->N; r.d = c->d; r.row0 = 0; r.nrows = np_; r.ncols = Np;
-    set_kernel_args(c, r);
-    r.diag_add = 0.; r.symmetric = 0;
-    r.delta_square = (n == c->N) ? 1 : 0;
-    r.max_sq = box_max_sq(c->box_test(), c->box_train());
-    r.out = R; r.ld = ldV;
+    const RbfArgs r = rbf_test_train(c, R, ldV);          // R = K(X*, X)
     HIP_TRY(launch_rbf(st, r));
     hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,
                        (int64_t)0, C, o_mu);                          // mu* = R (Y - P)^T

@@ -266,20 +266,9 @@ hipError_t launch_gram_tn(hipStream_t s, const double* V, int64_t ldv, int64_t r
     return hipGetLastError();
 }
 
-static void sparse_drop_other_state(gpmi_ctx* c) {
-    c->have_sparse = false;
-    c->have_factor = false;
-    c->have_laplace = c->have_softmax = false;
-    c->v_in_A = false;
-    c->have_vinv = false;
-    c->have_vside = false;
-    c->have_v = false;
-    c->post_in_A = c->post_in_P = false;
-}
-
 int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,
                     int method, double* value, int64_t* bad_pivot) {
-    if (!c->have_train) return fail_arg("gpmi_sparse_fit: no training set (call gpmi_set_train)");
+    if (!c->res.have_train) return fail_arg("gpmi_sparse_fit: no training set (call gpmi_set_train)");
     if (c->kind != 0) return fail_arg("gpmi_sparse_fit: squared-exponential kernel only (gpmi_set_kernel kind 0)");
     if (method != GPMI_SPARSE_VFE && method != GPMI_SPARSE_FITC)
         return fail_arg("gpmi_sparse_fit: method must be GPMI_SPARSE_VFE (0) or GPMI_SPARSE_FITC (1)");
@@ -292,7 +281,7 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     const int64_t N = c->N, d = c->d, Np = round_up(N, TILE);
     const int64_t mp = round_up(m, TILE), ldm = mp + c->ld_pad;
     const int64_t S = std::min(Np, c->sparse_slab ? round_up(c->sparse_slab, TILE) : DEFAULT_SLAB);
-    sparse_drop_other_state(c);
+    c->res.drop_fit();
     c->timers_reset({GPMI_T_SPARSE, GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR, GPMI_T_POSTCHOL, GPMI_T_CHOL});
     c->sig2 = sigma * sigma;
     c->coef = -.5 * (1 / (ell * ell));
@@ -349,13 +338,7 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     // L = chol(K_uu + j I)
     size_t sp = c->span_begin(GPMI_T_CHOL);
     {
-        RbfArgs r;
-        r.A = r.B = Zd;
-        r.nA = r.nB = m; r.d = d; r.row0 = 0; r.nrows = mp; r.ncols = mp;
-        set_kernel_args(c, r);
-        r.diag_add = jitter; r.symmetric = 1; r.delta_square = 1;
-        r.max_sq = box_max_sq(c->boxU, c->boxU);
-        r.out = Lm; r.ld = ldm;
+        const RbfArgs r = rbf_sym(c, Zd, m, c->boxU, jitter, mp, Lm, ldm);
         HIP_TRY(launch_rbf(st, r));
     }
     HIP_TRY(cholesky_inplace(c, Lm, ldm, mp, mp, info, false));
@@ -378,17 +361,10 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     HIP_TRY(hipMemsetAsync(g, 0, (size_t)mp * 8, st));
     HIP_TRY(hipMemsetAsync(acc, 0, 16 * 8, st));
 
-    const double max_sq = box_max_sq(c->box_train(), c->boxU);
     for (int64_t row0 = 0; row0 < Np; row0 += S) {
         const int64_t rows = std::min(S, Np - row0), nreal = std::min(rows, N - row0);
         sp = c->span_begin(GPMI_T_KS);
-        RbfArgs r;                              // K(X_slab, Z)
-        r.A = c->x_train(); r.B = Zd;
-        r.nA = N; r.nB = m; r.d = d; r.row0 = row0; r.nrows = rows; r.ncols = mp;
-        set_kernel_args(c, r);
-        r.diag_add = 0.; r.symmetric = 0; r.delta_square = 0;
-        r.max_sq = max_sq;
-        r.out = W; r.ld = ldm;
+        const RbfArgs r = rbf_cross(c, c->x_train(), N, c->box_train(), Zd, m, c->boxU, row0, rows, mp, W, ldm);   // K(X_slab, Z)
         HIP_TRY(launch_rbf(st, r));
         c->span_end(sp);
         sp = c->span_begin(GPMI_T_SOLVE_V);
@@ -435,13 +411,13 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     }
     if (bad_pivot) *bad_pivot = 0;
     if (value) *value = h_rec[0];
-    c->have_sparse = true;
+    c->res.fit_done(Fit::Sparse);
     return GPMI_OK;
 }
 
 int sparse_predict_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
-    if (!c->have_sparse) return fail_arg("gpmi_sparse_predict: no sparse fit resident (call gpmi_sparse_fit)");
-    if (!c->have_test) return fail_arg("gpmi_sparse_predict: no test set (call gpmi_set_test)");
+    if (!c->res.sparse()) return fail_arg("gpmi_sparse_predict: no sparse fit resident (call gpmi_sparse_fit)");
+    if (!c->res.have_test) return fail_arg("gpmi_sparse_predict: no test set (call gpmi_set_test)");
     Tuning tn = c->tune;
     tn.panel_fused = c->sp_fused;          // solve with the kind of leaves that produced the resident factors
     TuneScope tune_scope(&tn);
@@ -457,17 +433,10 @@ int sparse_predict_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
     const double* Lm = c->sp_L.as<double>();
     const double* Bm = c->sp_B.as<double>();
     const double* cvec = Bm + mp * ldm;
-    const double max_sq = box_max_sq(c->box_test(), c->boxU);
     for (int64_t r0 = 0; r0 < np_; r0 += chunk) {
         const int64_t rows = std::min(chunk, np_ - r0);
         size_t sp = c->span_begin(GPMI_T_KS);
-        RbfArgs r;                          // K(X*, Z)
-        r.A = c->x_test(); r.B = c->sp_Z.as<double>();
-        r.nA = n; r.nB = m; r.d = c->d; r.row0 = r0; r.nrows = rows; r.ncols = mp;
-        set_kernel_args(c, r);
-        r.diag_add = 0.; r.symmetric = 0; r.delta_square = 0;
-        r.max_sq = max_sq;
-        r.out = W; r.ld = ldm;
+        const RbfArgs r = rbf_cross(c, c->x_test(), n, c->box_test(), c->sp_Z.as<double>(), m, c->boxU, r0, rows, mp, W, ldm);   // K(X*, Z)
         HIP_TRY(launch_rbf(st, r));
         c->span_end(sp);
         sp = c->span_begin(GPMI_T_SOLVE_V);
@@ -498,7 +467,7 @@ int sparse_predict_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
 }
 
 int sparse_get_impl(gpmi_ctx* c, double* c_out, double* q_out) {
-    if (!c->have_sparse) return fail_arg("gpmi_sparse_get: no sparse fit resident (call gpmi_sparse_fit)");
+    if (!c->res.sparse()) return fail_arg("gpmi_sparse_get: no sparse fit resident (call gpmi_sparse_fit)");
     hipStream_t st = c->stream;
     if (c_out)
         HIP_TRY(hipMemcpyAsync(c_out, c->sp_B.as<double>() + c->sp_mp * c->sp_ld, (size_t)c->sp_m * 8, hipMemcpyDeviceToHost, st));
