@@ -8,6 +8,6 @@ Everything numerical runs in hand-written HIP kernels reached through the C-ABI
 of include/gpmi.h (libgpmi355x.so); there is no CPU fallback.
 """
 from .gp import GPContext, default_context  # noqa: F401
-from .GP_sparse_regression import choose_inducing, sparse_prediction  # noqa: F401
+from .GP_sparse_regression import choose_inducing, sparse_bound_and_gradient, sparse_prediction  # noqa: F401
 
-__all__ = ["GPContext", "default_context", "choose_inducing", "sparse_prediction"]
+__all__ = ["GPContext", "default_context", "choose_inducing", "sparse_prediction", "sparse_bound_and_gradient"]

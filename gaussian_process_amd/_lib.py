@@ -77,6 +77,7 @@ SIGNATURES = {
     "gpmi_sparse_fit": [_vp, _dp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(_i64)],
     "gpmi_sparse_predict_resident": [_vp, _dp, _dp, C.c_int],
     "gpmi_sparse_get": [_vp, _dp, _dp],
+    "gpmi_sparse_grad": [_vp, _dp, _dp, _dp, _dp, _dp],
     "gpmi_get_timers": [_vp, _dp, C.c_int],
     "gpmi_sync": [_vp],
     "gpmi_probe_mfma_f64": [_vp, _dp],

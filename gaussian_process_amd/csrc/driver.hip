@@ -318,6 +318,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     }
     if (with_post && std::isnan(jitter)) return fail_arg("gpmi_fit_predict_sample: jitter is NaN");
     c->res.drop_fit();                // a regression factorisation replaces whatever fit was resident
+    c->release_sparse_grad();
     int rc = ensure_train_buffers(c, with_test ? c->np_ : 0, form == 3);
     if (rc) return rc;
     hipStream_t s = c->stream;

@@ -77,7 +77,8 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
                        &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
-                       &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred})
+                       &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred,
+                       &c->sp_g0, &c->sp_g1, &c->sp_g2, &c->sp_gE, &c->sp_gpart, &c->sp_gvec})
         b->release();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -304,6 +305,7 @@ int gpmi_set_train(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const dou
     if (N <= 0 || d <= 0) return fail_arg("gpmi_set_train: N and d must be positive");
     HIP_TRY(hipSetDevice(c->device));
     c->res.drop_train();
+    c->release_sparse_grad();
     HIP_TRY(c->X.ensure((size_t)N * d * 8));
     HIP_TRY(c->y.ensure((size_t)N * 8));
     HIP_TRY(hipMemcpyAsync(c->X.p, X, (size_t)N * d * 8, hipMemcpyHostToDevice, c->stream));
@@ -1088,6 +1090,12 @@ int gpmi_sparse_get(gpmi_ctx* c, double* c_out, double* q_out) {
     if (!c) return fail_arg("gpmi_sparse_get: null context");
     HIP_TRY(hipSetDevice(c->device));
     return sparse_get_impl(c, c_out, q_out);
+}
+
+int gpmi_sparse_grad(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise, double* d_r, double* d_Z) {
+    if (!c) return fail_arg("gpmi_sparse_grad: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return sparse_grad_impl(c, d_ell, d_sigma, d_noise, d_r, d_Z);
 }
 
 int gpmi_get_timers(gpmi_ctx* c, double* stage_ms, int count) {

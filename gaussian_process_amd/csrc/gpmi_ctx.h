@@ -180,6 +180,14 @@ struct gpmi_ctx {
     int64_t sp_m = 0, sp_mp = 0, sp_ld = 0, sp_wrows = 0;
     Box boxU;                    // bounding box of the (scaled) inducing inputs
     DevBuf sp_Zraw, sp_Z, sp_L, sp_B, sp_W, sp_q, sp_vec, sp_part, sp_scr, sp_info, sp_pred;
+    // gpmi_sparse_grad: three sp_mp x sp_ld matrices, the slab-sized E, the chunks' partial sums and the vectors -- workspaces
+    // of its own, made at the first call, so that the resident fit above is only ever read.  They hold no state and go
+    // when something other than a sparse fit takes the sparse fit's place: a regression factorisation, a classifier's
+    // fit, a new training set (a sparse fit after a sparse fit, the tuner's step, keeps them).
+    DevBuf sp_g0, sp_g1, sp_g2, sp_gE, sp_gpart, sp_gvec;
+    void release_sparse_grad() {
+        for (DevBuf* b : {&sp_g0, &sp_g1, &sp_g2, &sp_gE, &sp_gpart, &sp_gvec}) b->release();
+    }
     // timers
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -317,6 +325,7 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
                     int method, double* value, int64_t* bad_pivot);
 int sparse_predict_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
 int sparse_get_impl(gpmi_ctx* c, double* c_out, double* q_out);
+int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise, double* d_r, double* d_Z);
 // B_lower (mp x mp, leading dimension ldb) += V^T V for the row-major slab V (rows x mp, leading dimension ldv; rows and
 // mp multiples of 128) on the matrix pipe; part: gram_part_doubles(rows, mp) doubles of workspace
 int64_t gram_part_doubles(int64_t rows, int64_t mp);

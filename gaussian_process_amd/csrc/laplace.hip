@@ -300,6 +300,7 @@ int classifier_fit_check(const gpmi_ctx* c, const char* api, const char* own, do
 
 int classifier_fit_begin(gpmi_ctx* c, double sigma, double ell, bool* chain) {
     c->res.drop_fit();                    // a classifier's factor replaces whatever was resident: no other state survives
+    c->release_sparse_grad();
     int rc = ensure_train_buffers(c, 0, false);
     if (rc) return rc;
     c->sig2 = sigma * sigma;

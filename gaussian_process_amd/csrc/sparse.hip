@@ -244,6 +244,173 @@ GramPlan gram_plan(int64_t rows, int64_t mp) {
     return p;
 }
 
+// ---- the gradient of the VFE bound -----------------------------------------------------------------------------------
+// With u = L_B^-T c, p = L^-T u, T = L^-T (I - B^-1) L^-1 / s, beta = (y - K_fu p) / s and
+// D_uu = -1/2 L^-T (B - 2 I + B^-1 + u u^T) L^-1 the derivatives of the bound w.r.t. K_fu and K_uu are
+// D_fu = K_fu T + beta p^T and D_uu, and every hyper-parameter and Z reach the bound through the squared distances:
+// with G = D o K only  sum G,  sum G (z_ik - z_jk)^2  per dimension k  and  sum_i G_ij (z_ik - z_jk)  per (j, k)  are
+// needed.  sparse_contract_kernel forms them for a block of rows (a slab of K_fu with E = W T, or K_uu with E = D_uu and
+// beta = 0), reading every element of W and of E once.
+//
+// grid (ceil(mp / 256), chunks of CT_ROWS rows); a wave owns 64 columns, a lane one column j: z_j, p_j and the 2 DW + 1
+// accumulators stay in registers, the chunk's x_i and beta_i are staged in LDS once and read back as broadcasts.  No
+// lane ever adds to another lane's sums, so the order of every sum is the row order; the chunks' partials
+// (part[chunk][component][column]) are added in chunk order by launch_sum_fixed.  Rows >= nreal are never read;
+// columns >= m write zeros.
+constexpr int CT_ROWS = 128;
+struct ContractArgs {
+    const double* W;          // rows x ld: the covariances
+    const double* E;          // rows x ld: dF/dK without the beta p^T term
+    int64_t ld, nreal;        // leading dimension of both, rows that count
+    const double* X;          // the rows' (scaled) inputs, nreal x d
+    const double* beta;       // nreal, or null for zero
+    const double* p;          // m
+    const double* Z;          // the columns' (scaled) inputs, m x d
+    int64_t m, mp;
+    int d;
+    double* part;             // [chunks][2 d + 1][mp]: sum G | sum G diff_k^2 (k < d) | sum G diff_k (k < d)
+};
+template <int DW>
+__global__ __launch_bounds__(256) void sparse_contract_kernel(ContractArgs a) {
+    __shared__ double xs[CT_ROWS * DW];
+    __shared__ double bs[CT_ROWS];
+    const int tid = threadIdx.x, d = a.d;
+    const int64_t i0 = (int64_t)blockIdx.y * CT_ROWS;
+    const int nrow = (int)(a.nreal - i0 < CT_ROWS ? a.nreal - i0 : CT_ROWS);
+    for (int e = tid; e < CT_ROWS * DW; e += 256) {
+        const int r = e / DW, k = e % DW;
+        xs[e] = (r < nrow && k < d) ? a.X[(i0 + r) * d + k] : 0.0;
+    }
+    if (tid < CT_ROWS) bs[tid] = (a.beta && tid < nrow) ? a.beta[i0 + tid] : 0.0;
+    __syncthreads();
+    const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+    if (j >= a.mp) return;                                     // a whole wave: mp is a multiple of 128
+    const bool real = j < a.m;
+    double zj[DW], sq[DW], dz[DW];
+#pragma unroll
+    for (int k = 0; k < DW; ++k) {
+        zj[k] = (real && k < d) ? a.Z[j * d + k] : 0.0;
+        sq[k] = 0.0;
+        dz[k] = 0.0;
+    }
+    const double pj = real ? a.p[j] : 0.0;
+    double sg = 0.0;
+    const double* Wp = a.W + i0 * a.ld + j;
+    const double* Ep = a.E + i0 * a.ld + j;
+    auto row = [&](int r, double w, double e) {
+        const double g = fma(bs[r], pj, e) * w;
+        sg += g;
+#pragma unroll
+        for (int k = 0; k < DW; ++k) {
+            const double df = xs[r * DW + k] - zj[k];
+            const double t = g * df;
+            dz[k] += t;
+            sq[k] = fma(t, df, sq[k]);
+        }
+    };
+    int r = 0;
+    for (; r + 4 <= nrow; r += 4) {
+        double w[4], e[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            w[q] = Wp[(int64_t)(r + q) * a.ld];
+            e[q] = Ep[(int64_t)(r + q) * a.ld];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) row(r + q, w[q], e[q]);
+    }
+    for (; r < nrow; ++r) row(r, Wp[(int64_t)r * a.ld], Ep[(int64_t)r * a.ld]);
+    double* P = a.part + (int64_t)blockIdx.y * (2 * d + 1) * a.mp + j;
+    P[0] = real ? sg : 0.0;
+#pragma unroll
+    for (int k = 0; k < DW; ++k)
+        if (k < d) {
+            P[(int64_t)(1 + k) * a.mp] = real ? sq[k] : 0.0;
+            P[(int64_t)(1 + d + k) * a.mp] = real ? dz[k] : 0.0;
+        }
+}
+
+// acc (2 d + 1 components x mp columns) += the contraction of one block of rows
+hipError_t launch_contract(hipStream_t s, const ContractArgs& a, double* acc) {
+    if (a.nreal <= 0 || a.mp <= 0) return hipSuccess;
+    if (a.d < 1 || a.d > 32 || a.mp % TILE) return hipErrorInvalidValue;
+    const int64_t chunks = (a.nreal + CT_ROWS - 1) / CT_ROWS;
+    if (chunks > 65535) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.mp + 255) / 256), (unsigned)chunks);
+    if (a.d <= 4) hipLaunchKernelGGL(sparse_contract_kernel<4>, grid, dim3(256), 0, s, a);
+    else if (a.d <= 8) hipLaunchKernelGGL(sparse_contract_kernel<8>, grid, dim3(256), 0, s, a);
+    else if (a.d <= 16) hipLaunchKernelGGL(sparse_contract_kernel<16>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(sparse_contract_kernel<32>, grid, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t n = (int64_t)(2 * a.d + 1) * a.mp;
+    return launch_sum_fixed(s, a.part, chunks, n, n, acc, 1.0, acc);
+}
+
+// dst = the lower triangle of src, zeros above it (what the fused panel kernels leave above a factor's diagonal goes)
+__global__ void sparse_tril_kernel(const double* __restrict__ src, double* __restrict__ dst, int64_t ld, int64_t n) {
+    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) dst[i * ld + j] = j <= i ? src[i * ld + j] : 0.0;
+}
+
+// rec[0] = tr B^-1 = -sum_{i < m} nBinv_ii, rec[1] = sum_{i < N} (sigma^2 - q_i), rec[2] = 0 (beta^T beta gathers there)
+__global__ __launch_bounds__(256) void sparse_grad_scalars_kernel(const double* __restrict__ nBinv, int64_t ld, int64_t m,
+                                                                  const double* __restrict__ q, int64_t N, double sig2,
+                                                                  double* __restrict__ rec) {
+    __shared__ double sh[4];
+    double v = 0.0;
+    for (int64_t i = threadIdx.x; i < m; i += 256) v -= nBinv[i * ld + i];
+    const double tr = wg_sum256(v, sh);
+    v = 0.0;
+    for (int64_t i = threadIdx.x; i < N; i += 256) v += sig2 - q[i];
+    const double tq = wg_sum256(v, sh);
+    if (threadIdx.x == 0) { rec[0] = tr; rec[1] = tq; rec[2] = 0.0; }
+}
+
+// In: nB = -B, nBinv = -B^-1 (what C -= A B^T leaves in a zeroed C).  Out, in place: the cores of D_uu and of -T,
+//   nB <- -1/2 (B - 2 I + B^-1 + u u^T),   nBinv <- (B^-1 - I) / s
+__global__ void sparse_grad_core_kernel(double* __restrict__ nB, double* __restrict__ nBinv, const double* __restrict__ u,
+                                        int64_t ld, int64_t n, double inv_s) {
+    const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const double b = -nB[i * ld + j], bi = -nBinv[i * ld + j], eye = i == j ? 1.0 : 0.0;
+    nB[i * ld + j] = -0.5 * (((b - 2.0 * eye) + bi) + u[i] * u[j]);
+    nBinv[i * ld + j] = (bi - eye) * inv_s;
+}
+
+// beta_i = (y_i - dot_i) / s for i < nreal, and *sum += sum beta_i^2: one workgroup, index order per thread
+__global__ __launch_bounds__(256) void sparse_beta_kernel(const double* __restrict__ y, const double* __restrict__ dot,
+                                                          int64_t nreal, double inv_s, double* __restrict__ beta,
+                                                          double* __restrict__ sum) {
+    __shared__ double sh[4];
+    double v = 0.0;
+    for (int64_t i = threadIdx.x; i < nreal; i += 256) {
+        const double b = (y[i] - dot[i]) * inv_s;
+        beta[i] = b;
+        v = fma(b, b, v);
+    }
+    const double t = wg_sum256(v, sh);
+    if (threadIdx.x == 0) *sum += t;
+}
+
+// rec[0] = sum_j (F + U)[0][j], rec[1 + k] = sum_j (F + U)[1 + k][j], dz[j][k] = F[1 + d + k][j] + 2 U[1 + d + k][j]
+// for the column sums F of the K_fu part and U of the K_uu part (the symmetric K_uu moves with z_j through both indices)
+__global__ __launch_bounds__(256) void sparse_grad_final_kernel(const double* __restrict__ F, const double* __restrict__ U,
+                                                                int64_t m, int64_t mp, int d, double* __restrict__ rec,
+                                                                double* __restrict__ dz) {
+    __shared__ double sh[4];
+    for (int comp = 0; comp <= d; ++comp) {
+        double v = 0.0;
+        for (int64_t j = threadIdx.x; j < m; j += 256) v += F[comp * mp + j] + U[comp * mp + j];
+        const double t = wg_sum256(v, sh);
+        if (threadIdx.x == 0) rec[comp] = t;
+    }
+    for (int64_t e = threadIdx.x; e < m * d; e += 256) {
+        const int64_t j = e / d, k = e % d;
+        dz[e] = F[(1 + d + k) * mp + j] + 2.0 * U[(1 + d + k) * mp + j];
+    }
+}
+
 }  // namespace
 
 int64_t gram_part_doubles(int64_t rows, int64_t mp) {
@@ -473,6 +640,154 @@ int sparse_get_impl(gpmi_ctx* c, double* c_out, double* q_out) {
         HIP_TRY(hipMemcpyAsync(c_out, c->sp_B.as<double>() + c->sp_mp * c->sp_ld, (size_t)c->sp_m * 8, hipMemcpyDeviceToHost, st));
     if (q_out) HIP_TRY(hipMemcpyAsync(q_out, c->sp_q.p, (size_t)c->N * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return GPMI_OK;
+}
+
+// The gradient of the VFE bound at the resident fit (include/gpmi.h: gpmi_sparse_grad).  The m-sized part runs on three
+// m_p x ld workspaces G0, G1, G2 and the slab-sized E; every product is C -= A B^T into a zeroed C on the routed GEMM,
+// so a chain of two products carries no sign.  Nothing of the fit is written: sp_W is a workspace already.
+int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise, double* d_r, double* d_Z) {
+    if (!c->res.sparse()) return fail_arg("gpmi_sparse_grad: no sparse fit resident (call gpmi_sparse_fit)");
+    if (c->sp_method != GPMI_SPARSE_VFE)
+        return fail_arg("gpmi_sparse_grad: the resident fit is FITC; only the gradient of the VFE bound is implemented");
+    if (c->d > 32) return fail_arg("gpmi_sparse_grad: at most 32 input dimensions");
+    Tuning tn = c->tune;
+    tn.panel_fused = c->sp_fused;          // solve with the kind of leaves that produced the resident factors
+    TuneScope tune_scope(&tn);
+    hipStream_t st = c->stream;
+    const int64_t N = c->N, Np = round_up(N, TILE), m = c->sp_m, mp = c->sp_mp, ldm = c->sp_ld, S = c->sp_wrows;
+    const int d = (int)c->d, ncomp = 2 * d + 1;
+    const double s = c->noise, inv_s = 1.0 / s;
+    const int64_t erows = std::max(S, mp), chunks = (erows + CT_ROWS - 1) / CT_ROWS, ncol = (int64_t)ncomp * mp;
+    const size_t mat = (size_t)mp * ldm * 8;
+    HIP_TRY(c->sp_g0.ensure(mat));
+    HIP_TRY(c->sp_g1.ensure(mat));
+    HIP_TRY(c->sp_g2.ensure(mat));
+    HIP_TRY(c->sp_gE.ensure((size_t)erows * ldm * 8));
+    HIP_TRY(c->sp_gpart.ensure((size_t)(chunks * ncol) * 8));
+    // sp_gvec: u | p | the slab's W p | beta | the column sums of the K_fu part | of the K_uu part | rec | dz
+    const int64_t nrec = round_up(d + 4, 2);
+    HIP_TRY(c->sp_gvec.ensure((size_t)(2 * mp + 2 * S + 2 * ncol + nrec + m * d) * 8));
+    double* G0 = c->sp_g0.as<double>();
+    double* G1 = c->sp_g1.as<double>();
+    double* G2 = c->sp_g2.as<double>();
+    double* E = c->sp_gE.as<double>();
+    double* part = c->sp_gpart.as<double>();
+    double* u = c->sp_gvec.as<double>();
+    double* p = u + mp;
+    double* dot = p + mp;
+    double* beta = dot + S;
+    double* colF = beta + S;
+    double* colU = colF + ncol;
+    double* rec = colU + ncol;
+    double* dz = rec + nrec;
+    double* W = c->sp_W.as<double>();
+    const double* Lm = c->sp_L.as<double>();
+    const double* Bm = c->sp_B.as<double>();
+    const double* cvec = Bm + mp * ldm;
+    const double* Zd = c->sp_Z.as<double>();
+    const dim3 egrid((unsigned)((mp + 255) / 256), (unsigned)mp);
+
+    // C (rows x mp) = -A B^T over K = mp
+    auto neg_product = [&](double* C, const double* A, const double* B, int64_t rows) -> hipError_t {
+        hipError_t e = hipMemsetAsync(C, 0, (size_t)rows * ldm * 8, st);
+        if (e != hipSuccess) return e;
+        GemmArgs g;
+        g.C = C; g.A = A; g.B = B;
+        g.ldc = g.lda = g.ldb = ldm;
+        g.M = rows; g.N = mp; g.K = mp;
+        g.mode = 0; g.lower = 0; g.diag_off = 0;
+        return launch_gemm_nt(st, g);
+    };
+    // V = F^-T (upper triangular) for a resident lower factor F, by the sweep on the identity
+    auto inverse_t = [&](const double* F, double* V) -> hipError_t {
+        hipError_t e = hipMemsetAsync(V, 0, mat, st);
+        if (e != hipSuccess) return e;
+        if ((e = launch_set_identity_diag(st, V, ldm, mp)) != hipSuccess) return e;
+        return solve_sweep_factor(c, F, ldm, mp, V, ldm, mp, true);
+    };
+
+    c->timers_reset({GPMI_T_SPARSE, GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR, GPMI_T_POSTCHOL, GPMI_T_CHOL});
+    const size_t sp_all = c->span_begin(GPMI_T_SPARSE);
+    // ---- the m-sized part: GPMI_T_CHOL
+    size_t sp = c->span_begin(GPMI_T_CHOL);
+    HIP_TRY(hipMemsetAsync(colF, 0, (size_t)(2 * ncol) * 8, st));
+    HIP_TRY(inverse_t(Bm, G0));                                            // G0 = L_B^-T
+    HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, cvec, u, nullptr));       // u = L_B^-T c
+    HIP_TRY(neg_product(G1, G0, G0, mp));                                  // G1 = -B^-1
+    hipLaunchKernelGGL(sparse_grad_scalars_kernel, dim3(1), dim3(256), 0, st, (const double*)G1, ldm, m,
+                       (const double*)c->sp_q.as<double>(), N, c->sig2, rec);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sparse_tril_kernel, egrid, dim3(256), 0, st, Bm, G0, ldm, mp);      // G0 = L_B
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(neg_product(G2, G0, G0, mp));                                  // G2 = -B
+    hipLaunchKernelGGL(sparse_grad_core_kernel, egrid, dim3(256), 0, st, G2, G1, (const double*)u, ldm, mp, inv_s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(inverse_t(Lm, G0));                                            // G0 = L^-T
+    HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, u, p, nullptr));          // p = L^-T u
+    HIP_TRY(neg_product(E, G0, G1, mp));
+    HIP_TRY(neg_product(G1, E, G0, mp));                                   // G1 = -T
+    HIP_TRY(neg_product(E, G0, G2, mp));
+    HIP_TRY(neg_product(G2, E, G0, mp));                                   // G2 = D_uu
+    c->span_end(sp);
+
+    ContractArgs ca;
+    ca.ld = ldm; ca.p = p; ca.Z = Zd; ca.m = m; ca.mp = mp; ca.d = d; ca.part = part;
+    // ---- the K_uu part: W = K(Z, Z) without the jitter, E = D_uu, beta = 0
+    sp = c->span_begin(GPMI_T_KS);
+    {
+        const RbfArgs r = rbf_cross(c, Zd, m, c->boxU, Zd, m, c->boxU, 0, mp, mp, G0, ldm);
+        HIP_TRY(launch_rbf(st, r));
+    }
+    c->span_end(sp);
+    sp = c->span_begin(GPMI_T_MEANVAR);
+    ca.W = G0; ca.E = G2; ca.nreal = m; ca.X = Zd; ca.beta = nullptr;
+    HIP_TRY(launch_contract(st, ca, colU));
+    c->span_end(sp);
+
+    // ---- the K_fu part, slab by slab
+    for (int64_t row0 = 0; row0 < Np; row0 += S) {
+        const int64_t rows = std::min(S, Np - row0), nreal = std::min(rows, N - row0);
+        sp = c->span_begin(GPMI_T_KS);
+        const RbfArgs r = rbf_cross(c, c->x_train(), N, c->box_train(), Zd, m, c->boxU, row0, rows, mp, W, ldm);   // K(X_slab, Z)
+        HIP_TRY(launch_rbf(st, r));
+        c->span_end(sp);
+        sp = c->span_begin(GPMI_T_SOLVE_V);
+        HIP_TRY(launch_row_dots(st, W, ldm, nreal, mp, p, dot, nullptr));
+        hipLaunchKernelGGL(sparse_beta_kernel, dim3(1), dim3(256), 0, st, (const double*)(c->y.as<double>() + row0),
+                           (const double*)dot, nreal, inv_s, beta, rec + 2);
+        HIP_TRY(hipGetLastError());
+        c->span_end(sp);
+        sp = c->span_begin(GPMI_T_POSTCHOL);
+        HIP_TRY(neg_product(E, W, G1, rows));                              // E = W T
+        c->span_end(sp);
+        sp = c->span_begin(GPMI_T_MEANVAR);
+        ca.W = W; ca.E = E; ca.nreal = nreal; ca.X = c->x_train() + row0 * d; ca.beta = beta;
+        HIP_TRY(launch_contract(st, ca, colF));
+        c->span_end(sp);
+    }
+    hipLaunchKernelGGL(sparse_grad_final_kernel, dim3(1), dim3(256), 0, st, (const double*)colF, (const double*)colU, m, mp,
+                       d, rec + 3, dz);
+    HIP_TRY(hipGetLastError());
+    c->span_end(sp_all);
+    std::vector<double> h((size_t)(nrec + m * d));
+    HIP_TRY(hipMemcpyAsync(h.data(), rec, (d_Z ? h.size() : (size_t)nrec) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+
+    const double sigma = c->sigma, l = c->ell, l2 = l * l;
+    const double sum_g = h[3];
+    double sum_sq = 0.0;
+    for (int k = 0; k < d; ++k) sum_sq += h[4 + k];
+    if (d_ell) *d_ell = sum_sq / (l2 * l);
+    if (d_sigma) *d_sigma = (2.0 / sigma) * sum_g - (double)N * sigma / s;
+    if (d_noise) *d_noise = -((double)(N - m) + h[0]) / (2.0 * s) + 0.5 * h[2] + h[1] / (2.0 * s * s);
+    for (int k = 0; k < d; ++k) {
+        const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
+        if (d_r) d_r[k] = h[4 + k] / (l2 * rk);
+        if (d_Z)
+            for (int64_t j = 0; j < m; ++j) d_Z[j * d + k] = h[(size_t)(nrec + j * d + k)] / (l2 * rk);
+    }
     return GPMI_OK;
 }
 

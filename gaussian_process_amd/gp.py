@@ -463,8 +463,19 @@ class GPContext:
         O(m^2 + N d) device memory, for N far beyond an N x N covariance.  method "vfe" returns Titsias' collapsed lower
         bound of the log marginal likelihood, "fitc" the log likelihood log N(y | 0, Q_ff + diag(K_ff - Q_ff) + noise I).
         jitter is added to the diagonal of K(Z, Z).  The factors stay on the device for sparse_predict."""
-        X, Z, method_id = sparse_args(X, Z, method)
+        X, Z, _ = sparse_args(X, Z, method)
         self._set_train_ard(X, y, lengthscales)
+        return self.sparse_fit_resident(Z, sigma, l, noise_var, method=method, jitter=jitter)
+
+    def sparse_fit_resident(self, Z, sigma, l, noise_var, *, method="vfe", jitter=1e-6):
+        """sparse_fit on the training set and the lengthscales the context already holds (set_train, set_lengthscales):
+        nothing is uploaded but Z, which is what a tuner's step wants."""
+        if method not in _lib.SPARSE_METHODS:
+            raise ValueError("method must be one of %s, got %r" % (sorted(_lib.SPARSE_METHODS), method))
+        method_id = _lib.SPARSE_METHODS[method]
+        Z = as_f64(Z, 2, "Z")
+        if Z.shape[1] != self.d:
+            raise ValueError("Z has d=%d but the training set has d=%d" % (Z.shape[1], self.d))
         val = C.c_double()
         bad = C.c_int64()
         st = self._lib.gpmi_sparse_fit(self._h, ptr(Z), Z.shape[0], scalar(sigma, "sigma"), scalar(l, "l"),
@@ -488,6 +499,18 @@ class GPContext:
         q = np.empty(self.N)
         check(self._lib.gpmi_sparse_get(self._h, ptr(c), ptr(q)))
         return c, q
+
+    def sparse_grad(self, want_Z=True):
+        """Gradient of the VFE bound at the resident sparse fit (gpmi_sparse_grad): a dict with "l", "sigma", "noise"
+        (floats), "r" (d,) -- w.r.t. the context's lengthscales, at r = 1 when it has none -- and "Z" (m, d) -- w.r.t. the
+        inducing inputs as they were passed to sparse_fit; "Z" is None when want_Z is false."""
+        m = int(getattr(self, "m_inducing", 0))
+        dl, ds, dn = C.c_double(), C.c_double(), C.c_double()
+        d_r = np.empty(self.d)
+        d_Z = np.empty((m, self.d)) if want_Z else None
+        check(self._lib.gpmi_sparse_grad(self._h, C.byref(dl), C.byref(ds), C.byref(dn), ptr(d_r),
+                                         ptr(d_Z) if want_Z else None))
+        return {"l": dl.value, "sigma": ds.value, "noise": dn.value, "r": d_r, "Z": d_Z}
 
     # ---- batched LML ----------------------------------------------------------------
     def lml_batch(self, triples):

@@ -300,10 +300,14 @@ def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOI
     return np.float64(lml), d_r, d_sigma, d_noise
 
 
-def _log_ascent(value, gradient, theta, max_iter, tol):
-    """The accept / halve / step-carry ascent on the logarithms of positive parameters that tune_hyperparms_ard and
-    tune_hyperparms_loo share.  value(theta) -> the criterion at exp(theta), leaving its factorisation resident (-inf
-    where K + sI is not positive definite); gradient() -> its derivatives w.r.t. exp(theta) at the resident point.
+def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=False):
+    """The accept / halve / step-carry ascent on the logarithms of positive parameters that tune_hyperparms_ard,
+    tune_hyperparms_loo and tune_hyperparms_sparse share.  value(theta) -> the criterion at exp(theta), leaving its
+    factorisation resident (-inf where K + sI is not positive definite); gradient() -> its derivatives w.r.t. exp(theta)
+    at the resident point.  n_log: only the first n_log entries of theta are logarithms, the others are plain
+    coordinates (the inducing inputs) whose entries of gradient() are used as they are; None: all of them.  monotone: a
+    trial that is still lower after the last halving is not accepted -- the ascent stops where it stands -- so the values
+    of the accepted points never decrease (without it the last trial is accepted, as the two older tuners always did).
     -> (theta reached, its value, the values of every accepted point, the initial one first)."""
     cur = value(theta)
     if not np.isfinite(cur):
@@ -311,7 +315,8 @@ def _log_ascent(value, gradient, theta, max_iter, tol):
     trace = [cur]
     step = None
     for _ in range(int(max_iter)):
-        g = gradient() * np.exp(theta)
+        jac = np.exp(theta) if n_log is None else np.concatenate([np.exp(theta[:n_log]), np.ones(theta.size - n_log)])
+        g = gradient() * jac
         gmax = float(np.max(np.abs(g)))
         if not np.isfinite(gmax) or gmax == 0.0:
             break
@@ -323,7 +328,7 @@ def _log_ascent(value, gradient, theta, max_iter, tol):
             if new >= cur or halving == ARD_MAX_HALVINGS:
                 break
             step *= 0.5
-        if not np.isfinite(new):             # twenty halvings and still no factor: stay where the last one was
+        if not np.isfinite(new) or (monotone and new < cur):   # twenty halvings and still no factor: stay where the last one was
             value(theta)
             break
         theta = trial
@@ -427,3 +432,56 @@ def tune_hyperparms_loo(X_train, y_train, *, sigma=1.0, l=1.0, noise_var=NOISE_V
     theta, loo, trace = _log_ascent(value, lambda: np.asarray(ctx.loo_grad()), np.log([l, sigma, noise_var]), max_iter, tol)
     p = np.exp(theta)
     return float(p[0]), float(p[1]), float(p[2]), np.float64(loo), np.asarray(trace)
+
+
+# ---------------------------------------------------------------------------------------
+# Sparse regression: the collapsed variational bound (VFE) over the hyper-parameters and the inducing inputs, with the
+# gradient of gpmi_sparse_grad.  The reference has neither.
+# ---------------------------------------------------------------------------------------
+def tune_hyperparms_sparse(X_train, y_train, Z, *, sigma=1.0, lengthscales=None, noise_var=NOISE_VAR, optimise_Z=True,
+                           max_iter=100, tol=1e-6, jitter=1e-6, ctx=None):
+    """Maximise the VFE bound of sparse GP regression over (lengthscales, sigma, noise_var) and -- optimise_Z -- the
+    inducing inputs, by the ascent of tune_hyperparms_ard (the same loop): the positive parameters move on their
+    logarithms, Z in its plain coordinates.  A trial point that lowers the bound, or at which K_uu + jitter I or B is
+    not positive definite, halves the step; one that is still lower after the last halving ends the ascent unaccepted, so
+    the bound never decreases along the trace.
+
+    :param Z: (m, d) initial inducing inputs (choose_inducing draws a random subset)
+    :param lengthscales: initial per-dimension lengthscales (default: all 1)
+    :return: (lengthscales (d,), sigma, noise_var, Z (m, d), bound, trace): the parameters reached, their bound and the
+             bound of every accepted point, the initial one first.  The context is left with those lengthscales and
+             their sparse fit.
+    """
+    from .gp import sparse_args
+    ctx = ctx or default_context()
+    X_train, Z, _ = sparse_args(X_train, Z, "vfe")
+    m, d = Z.shape
+    ls = np.ones(d) if lengthscales is None else np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy()
+    if ls.shape[0] != d or not np.all(np.isfinite(ls)) or np.any(ls <= 0):
+        raise ValueError("lengthscales must be %d finite positive numbers" % d)
+    if not (sigma > 0 and noise_var > 0):
+        raise ValueError("sigma and noise_var must be positive (the ascent runs on their logarithms)")
+    Z0 = Z.copy()
+    ctx.set_train(X_train, y_train)                 # once: every step below fits on the resident training set
+    n_log = d + 2
+    theta = np.concatenate([np.log(np.concatenate([ls, [float(sigma), float(noise_var)]])),
+                            Z0.reshape(-1) if optimise_Z else []])
+
+    def inducing(th):
+        return np.ascontiguousarray(th[n_log:].reshape(m, d)) if optimise_Z else Z0
+
+    def value(th):
+        ctx.set_lengthscales(np.exp(th[:d]))
+        try:
+            return float(ctx.sparse_fit_resident(inducing(th), np.exp(th[d]), 1.0, np.exp(th[d + 1]), method="vfe",
+                                                 jitter=jitter))
+        except np.linalg.LinAlgError:
+            return -np.inf
+
+    def gradient():
+        g = ctx.sparse_grad(want_Z=optimise_Z)      # common l = 1: "r" is the derivative w.r.t. the lengthscales
+        return np.concatenate([g["r"], [g["sigma"], g["noise"]], g["Z"].reshape(-1) if optimise_Z else []])
+
+    theta, bound, trace = _log_ascent(value, gradient, theta, max_iter, tol, n_log=n_log, monotone=True)
+    return (np.exp(theta[:d]), float(np.exp(theta[d])), float(np.exp(theta[d + 1])), inducing(theta).copy(),
+            np.float64(bound), np.asarray(trace))

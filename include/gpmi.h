@@ -345,6 +345,33 @@ int gpmi_sparse_fit(gpmi_ctx* ctx, const double* Z, int64_t m, double sigma, dou
 int gpmi_sparse_predict_resident(gpmi_ctx* ctx, double* mu, double* out2, int want_sd);
 /* c (m doubles) and q (N doubles) of the resident sparse fit; either may be NULL.  For tests and small N. */
 int gpmi_sparse_get(gpmi_ctx* ctx, double* c_out, double* q_out);
+/* Gradient of the VFE bound F that gpmi_sparse_fit returned, at the resident fit, w.r.t. ell, sigma, noise_var, the
+ * context's lengthscales r (d doubles; without lengthscales the derivative at r = 1) and the inducing inputs Z as the
+ * caller passed them (m x d, row-major, unscaled).  Every output may be NULL.  With s = noise_var, z = x / r, K0_uu = K_uu
+ * without the jitter (a constant: the diagonal of K_uu contributes through sigma^2 only) and
+ *   u = L_B^-T c,  p = L^-T u,  T = L^-T (I - B^-1) L^-1 / s,  beta = (y - K_fu p) / s,
+ *   D_fu = K_fu T + beta p^T  (N x m, never held),  D_uu = -1/2 L^-T (B - 2 I + B^-1 + u u^T) L^-1,
+ *   G_fu = D_fu o K_fu,  G_uu = D_uu o K0_uu:
+ *   *d_sigma  = (2 / sigma) (sum G_fu + sum G_uu) - N sigma / s
+ *   *d_ell    = (sum_ij G_fu,ij |z_i - z_j|^2 + sum_jj' G_uu,jj' |z_j - z_j'|^2) / ell^3
+ *   d_r[k]    = (sum_ij G_fu,ij (z_ik - z_jk)^2 + sum_jj' G_uu,jj' (z_jk - z_j'k)^2) / (ell^2 r_k)
+ *   *d_noise  = -(N - m + tr B^-1) / (2 s) + 1/2 beta^T beta + sum_i (sigma^2 - q_i) / (2 s^2)
+ *   d_Z[j][k] = (sum_i G_fu,ij (z_ik - z_jk) + 2 sum_j' G_uu,jj' (z_j'k - z_jk)) / (ell^2 r_k)
+ * so sum_k r_k d_r[k] = ell *d_ell.  Device schedule: L_B^-T and L^-T by the sweep on the identity, B^-1, B = L_B L_B^T, T
+ * and D_uu by the routed GEMM (O(m^3)); then the training rows pass once more in slabs of the fit's size: K(X_slab, Z),
+ * beta, E = W T on the routed GEMM (2 N m^2 flops) and one contraction kernel that reads every element of W and E once;
+ * K_uu passes through the same kernel with E = D_uu.  Every sum runs in a fixed order without atomics: bitwise
+ * reproducible from run to run at one slab size.  One host synchronisation.  O(N m^2), the order of the fit.
+ *   GPMI_ERR_BAD_ARG: no sparse fit resident; the resident fit is FITC (its gradient is not implemented); d > 32 (the
+ *                     contraction keeps a column's 2 d + 1 sums in registers; there is no pass loop over dimensions).
+ * The resident fit is only read -- gpmi_sparse_predict_resident and gpmi_sparse_get return the same bits afterwards; the
+ * slab workspace that prediction also overwrites is reused.  The m x m temporaries live in workspaces of the call's own,
+ * 8 (max(S, m_p) ld + 3 m_p ld + chunks m_p (2 d + 1)) bytes with chunks = ceil(max(S, m_p) / 128), made at the first call
+ * and freed when a regression factorisation, a Laplace or softmax fit or gpmi_set_train takes the sparse fit's place (a
+ * sparse fit after a sparse fit keeps them: a tuner's step allocates nothing).  Timers: GPMI_T_SPARSE the whole span (it replaces the fit's), of which
+ * GPMI_T_CHOL the m-sized part, GPMI_T_KS the covariance builds, GPMI_T_SOLVE_V beta, GPMI_T_POSTCHOL the products W T and
+ * GPMI_T_MEANVAR the contractions. */
+int gpmi_sparse_grad(gpmi_ctx* ctx, double* d_ell, double* d_sigma, double* d_noise, double* d_r, double* d_Z);
 
 int gpmi_get_timers(gpmi_ctx* ctx, double* stage_ms, int count);
 /* block the host until everything queued on the context has finished */
