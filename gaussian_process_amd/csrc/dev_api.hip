@@ -119,9 +119,8 @@ int gpmi_dev_gemm_nt(void* stream, double* C_dev, int64_t ldc, const double* A_d
     if (!C_dev || !A_dev || !B_dev) return fail_arg("gpmi_dev_gemm_nt: null pointer");
     if (M < 0 || N < 0 || K < 0 || M % TILE || N % IB || K % 16 || ldc % 2 || lda % 2 || ldb % 2)
         return fail_arg("gpmi_dev_gemm_nt: M%128, N%64, K%16 must be 0");
-    GemmArgs g;
-    g.C = C_dev; g.A = A_dev; g.B = B_dev; g.ldc = ldc; g.lda = lda; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.mode = 0; g.lower = lower; g.diag_off = diag_off;
+    GemmArgs g = gemm_minus(C_dev, ldc, A_dev, lda, B_dev, ldb, M, N, K);
+    g.lower = lower; g.diag_off = diag_off;       // as given, whatever the caller passes for either
     HIP_TRY(launch_gemm_nt((hipStream_t)stream, g));
     return GPMI_OK;
 }
@@ -133,9 +132,7 @@ int gpmi_dev_gemm_nt_rowmap(void* stream, double* C_dev, int64_t ldc, const doub
     if (M < 0 || N < 0 || K < 0 || M % TILE || N % IB || K % 16 || ldc % 2 || lda % 2 || ldb % 2 ||
         row_block_rows <= 0 || row_block_rows % TILE)
         return fail_arg("gpmi_dev_gemm_nt_rowmap: M%128, N%64, K%16, row_block_rows%128 must be 0");
-    GemmArgs g;
-    g.C = C_dev; g.A = A_dev; g.B = B_dev; g.ldc = ldc; g.lda = lda; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.mode = 0; g.lower = 0; g.diag_off = 0;
+    GemmArgs g = gemm_minus(C_dev, ldc, A_dev, lda, B_dev, ldb, M, N, K);
     g.row_ncols = row_ncols_dev; g.row_block_tiles = (int)(row_block_rows / TILE);
     HIP_TRY(launch_gemm_nt((hipStream_t)stream, g));
     return GPMI_OK;
@@ -151,9 +148,7 @@ int gpmi_dev_gemm_nt_rowmap_host(void* stream, double* C_dev, int64_t ldc, const
     if (M < 0 || N < 0 || K < 0 || M % TILE || N % IB || K % 16 || ldc % 2 || lda % 2 || ldb % 2 ||
         row_block_rows <= 0 || row_block_rows % TILE || row_bands * row_block_rows < M)
         return fail_arg("gpmi_dev_gemm_nt_rowmap_host: M%128, N%64, K%16, row_block_rows%128 must be 0 and the map must cover M");
-    GemmArgs g;
-    g.C = C_dev; g.A = A_dev; g.B = B_dev; g.ldc = ldc; g.lda = lda; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.mode = 0; g.lower = 0; g.diag_off = 0;
+    GemmArgs g = gemm_minus(C_dev, ldc, A_dev, lda, B_dev, ldb, M, N, K);
     g.row_ncols = row_ncols_dev; g.row_block_tiles = (int)(row_block_rows / TILE);
     g.row_ncols_host = row_ncols_host; g.row_bands = (int)row_bands;
     HIP_TRY(launch_gemm_nt((hipStream_t)stream, g));
@@ -176,9 +171,7 @@ int gpmi_dev_gemm_nt_blocks(void* stream, double* C_dev, int64_t ldc, const doub
         return fail_arg("gpmi_dev_gemm_nt_blocks: the row map needs both its device and its host copy");
     if (row_ncols_dev && (row_block_rows <= 0 || row_block_rows % TILE || row_bands * row_block_rows < M))
         return fail_arg("gpmi_dev_gemm_nt_blocks: row_block_rows%128 must be 0 and the map must cover M");
-    GemmArgs g;
-    g.C = C_dev; g.A = A_dev; g.B = B_dev; g.ldc = ldc; g.lda = lda; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.mode = 0; g.lower = 0; g.diag_off = 0;
+    GemmArgs g = gemm_minus(C_dev, ldc, A_dev, lda, B_dev, ldb, M, N, K);
     g.b_block_off = b_block_off_dev; g.b_block_rows = b_block_rows;
     if (row_ncols_dev) {
         g.row_ncols = row_ncols_dev; g.row_block_tiles = (int)(row_block_rows / TILE);

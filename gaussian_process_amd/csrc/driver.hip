@@ -45,13 +45,8 @@ hipError_t panel_rec(hipStream_t s, double* A, int64_t ld, int64_t mrows, int64_
         // not a multiple of 128) lie above the diagonal of the updated columns and are never read.
         const int64_t c0 = off + h;
         const int64_t r0 = c0 / TILE * TILE;
-        GemmArgs g;
-        g.C = A + r0 * ld + c0;
-        g.A = A + r0 * ld + off;
-        g.B = A + c0 * ld + off;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = mrows - r0; g.N = w - h; g.K = h;
-        g.mode = 0; g.lower = 1; g.diag_off = r0 - c0;
+        const GemmArgs g = gemm_minus_lower(A + r0 * ld + c0, ld, A + r0 * ld + off, ld, A + c0 * ld + off, ld, mrows - r0,
+                                            w - h, h, r0 - c0);
         if ((e = launch_gemm_nt(s, g)) != hipSuccess) return e;
     }
     return panel_rec(s, A, ld, mrows, off + h, w - h, col_offset, info);
@@ -75,13 +70,7 @@ hipError_t trsm_rec(hipStream_t s, const double* L, int64_t ldl, double* X, int6
     }
     const int64_t h = (w / 2) / leaf * leaf;
     if ((e = trsm_rec(s, L, ldl, X, ldx, m, off, h)) != hipSuccess) return e;
-    GemmArgs g;
-    g.C = X + off + h;
-    g.A = X + off;
-    g.B = L + (off + h) * ldl + off;
-    g.ldc = g.lda = ldx; g.ldb = ldl;
-    g.M = m; g.N = w - h; g.K = h;
-    g.mode = 0; g.lower = 0; g.diag_off = 0;
+    const GemmArgs g = gemm_minus(X + off + h, ldx, X + off, ldx, L + (off + h) * ldl + off, ldl, m, w - h, h);
     if ((e = launch_gemm_nt(s, g)) != hipSuccess) return e;
     return trsm_rec(s, L, ldl, X, ldx, m, off + h, w - h);
 }
@@ -147,13 +136,8 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
     // time twice; (a) is launched under the generic symbol and timed with the panel it belongs to.
     auto trail = [&](hipStream_t st, bool counted, int64_t r0, int64_t c0, int64_t k, int64_t nb, int64_t ncol_upd) -> hipError_t {
         // C = A[r0.., c0..c0+ncol_upd) -= A[r0.., k..k+nb) * A[c0.., k..k+nb)^T, lower part
-        GemmArgs g;
-        g.C = A + r0 * ld + c0;
-        g.A = A + r0 * ld + k;
-        g.B = A + c0 * ld + k;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = nrows - r0; g.N = ncol_upd; g.K = nb;
-        g.mode = 0; g.lower = 1; g.diag_off = r0 - c0;
+        GemmArgs g = gemm_minus_lower(A + r0 * ld + c0, ld, A + r0 * ld + k, ld, A + c0 * ld + k, ld, nrows - r0, ncol_upd,
+                                      nb, r0 - c0);
         g.role = counted ? 1 : 0;
         // the roofline figures are those of the LDS-DMA kernel: the last, small updates that
         // run on the first-generation kernel are timed into the scratch slot
@@ -194,11 +178,9 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
                 if ((e = trsm_block(follow->vs, A + k * ld + k, ld, follow->V + k, follow->ldv, follow->m, nb)) != hipSuccess) return e;
             }
             if (r0 < ncols) {
-                GemmArgs g;   // V[:, r0..) -= V[:, k..k+nb) * L[r0.., k..k+nb)^T
-                g.C = follow->V + r0; g.A = follow->V + k; g.B = A + r0 * ld + k;
-                g.ldc = g.lda = follow->ldv; g.ldb = ld;
-                g.M = follow->m; g.N = ncols - r0; g.K = nb;
-                g.mode = 0; g.lower = 0; g.diag_off = 0;
+                // V[:, r0..) -= V[:, k..k+nb) * L[r0.., k..k+nb)^T
+                const GemmArgs g = gemm_minus(follow->V + r0, follow->ldv, follow->V + k, follow->ldv, A + r0 * ld + k, ld,
+                                              follow->m, ncols - r0, nb);
                 SharingScope update_forms(sharing().with_panel_slack(false));       // the following rows keep their forms
                 if ((e = launch_gemm_nt(follow->vs, g)) != hipSuccess) return e;
             }
@@ -432,12 +414,9 @@ hipError_t solve_sweep_factor(gpmi_ctx* c, const double* A, int64_t ld, int64_t 
     SharingScope shallow(!la ? sharing() : m >= 2048 ? Sharing::beside_update() : sharing().and_chip_shared());
     if (la && (e = c->order(sm, sp_)) != hipSuccess) return e;
     auto update = [&](int64_t c0, int64_t k, int64_t nb, int64_t ncol_upd) -> hipError_t {
-        GemmArgs g;   // V[:, c0..c0+ncol_upd) -= V[:, k..k+nb) * L[c0.., k..k+nb)^T
-        g.C = V + c0; g.A = V + k; g.B = A + c0 * ld + k;
-        g.ldc = g.lda = ldv; g.ldb = ld;
-        g.M = tri ? std::min(m, k + nb) : m; g.N = ncol_upd; g.K = nb;
-        g.mode = 0; g.lower = 0; g.diag_off = 0;
-        return launch_gemm_nt(sm, g);
+        // V[:, c0..c0+ncol_upd) -= V[:, k..k+nb) * L[c0.., k..k+nb)^T
+        return launch_gemm_nt(sm, gemm_minus(V + c0, ldv, V + k, ldv, A + c0 * ld + k, ld, tri ? std::min(m, k + nb) : m,
+                                             ncol_upd, nb));
     };
     for (int64_t k = 0; k < Np; k += NB) {
         const int64_t nb = std::min<int64_t>(NB, Np - k);
@@ -455,6 +434,27 @@ hipError_t solve_sweep_factor(gpmi_ctx* c, const double* A, int64_t ld, int64_t 
         if (r0 + nbn < Np && (e = update(r0 + nbn, k, nb, Np - r0 - nbn)) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// V = F^-T (upper triangular) for a resident lower factor F (n x n): the sweep on the identity.  Columns >= n of V are
+// neither written nor read, here or by any reader of the result.
+hipError_t inverse_transposed(gpmi_ctx* c, const double* F, int64_t ldf, int64_t n, double* V, int64_t ldv) {
+    hipError_t e = launch_fill_rows(c->stream, V, ldv, n, n, 0.0);
+    if (e != hipSuccess) return e;
+    if ((e = launch_set_identity_diag(c->stream, V, ldv, n)) != hipSuccess) return e;
+    return solve_sweep_factor(c, F, ldf, n, V, ldv, n, true);
+}
+
+// Out = -V V^T on the lower tiles for an upper triangular V (n x n, both with leading dimension ld), one launch per row
+// block: row block r0 of V is zero left of column r0, so the product starts there
+hipError_t neg_gram_lower(gpmi_ctx* c, const double* V, double* Out, int64_t ld, int64_t n) {
+    hipError_t e = launch_fill_rows(c->stream, Out, ld, n, n, 0.0);
+    const int64_t NB = c->block(n);
+    for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += NB) {
+        const int64_t nb = std::min<int64_t>(NB, n - r0);
+        e = launch_gemm_nt(c->stream, gemm_minus_lower(Out + r0 * ld, ld, V + r0 * ld + r0, ld, V + r0, ld, nb, r0 + nb, n - r0, r0));
+    }
+    return e;
 }
 
 }  // namespace gpmi

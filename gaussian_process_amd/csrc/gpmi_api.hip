@@ -1,6 +1,6 @@
-// C-ABI of libgpmi355x.so (see include/gpmi.h) and the single-GPU drivers:
-// blocked right-looking Cholesky, the TRSM sweep for v = L^-1 K_s, and the
-// glue that keeps the reference's call surface (GP_regression.py:109-156,
+// C-ABI of libgpmi355x.so (see include/gpmi.h): context lifetime, options, uploads, the covariance calls, the getters,
+// the batch of LML evaluations, and the shims in front of the models' *_impl functions (driver.hip, regress.hip,
+// laplace.hip, softmax.hip, sparse.hip) that keep the reference's call surface (GP_regression.py:109-156,
 // tune_hyperparms_regression.py:292-313) reachable through plain C.
 //
 // Data layout in HBM (one context):
@@ -28,6 +28,25 @@ TuneScope::TuneScope(const Tuning* t) : prev(t_tuning) { t_tuning = t; }
 TuneScope::~TuneScope() { t_tuning = prev; }
 static thread_local Sharing t_sharing;
 Sharing& sharing() { return t_sharing; }
+
+// z = x / r for the training / test inputs of a context with per-dimension lengthscales (the raw inputs stay resident:
+// a tuner that changes r every iteration uploads d doubles, not N d)
+int ard_rescale_train(gpmi_ctx* c) {
+    if (!c->ard()) return GPMI_OK;
+    HIP_TRY(c->Xz.ensure((size_t)c->N * c->d * 8));
+    HIP_TRY(launch_scale_inputs(c->stream, c->X.as<double>(), c->ard_rdev.as<double>(), c->N, c->d, c->Xz.as<double>()));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    box_scale(c->boxX, c->ard_r, c->boxZ);
+    return GPMI_OK;
+}
+int ard_rescale_test(gpmi_ctx* c) {
+    if (!c->ard()) return GPMI_OK;
+    HIP_TRY(c->Xsz.ensure((size_t)c->n * c->d * 8));
+    HIP_TRY(launch_scale_inputs(c->stream, c->Xs.as<double>(), c->ard_rdev.as<double>(), c->n, c->d, c->Xsz.as<double>()));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    box_scale(c->boxXs, c->ard_r, c->boxZs);
+    return GPMI_OK;
+}
 }
 
 extern "C" {
@@ -392,79 +411,11 @@ int gpmi_get_factor_block(gpmi_ctx* c, int64_t r0, int64_t r1, int64_t c0, int64
     return GPMI_OK;
 }
 
-}  // extern "C"
-
-// z = x / r for the training / test inputs of a context with per-dimension lengthscales (the raw inputs stay resident:
-// a tuner that changes r every iteration uploads d doubles, not N d)
-int gpmi::ard_rescale_train(gpmi_ctx* c) {
-    if (!c->ard()) return GPMI_OK;
-    HIP_TRY(c->Xz.ensure((size_t)c->N * c->d * 8));
-    HIP_TRY(launch_scale_inputs(c->stream, c->X.as<double>(), c->ard_rdev.as<double>(), c->N, c->d, c->Xz.as<double>()));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    box_scale(c->boxX, c->ard_r, c->boxZ);
-    return GPMI_OK;
-}
-int gpmi::ard_rescale_test(gpmi_ctx* c) {
-    if (!c->ard()) return GPMI_OK;
-    HIP_TRY(c->Xsz.ensure((size_t)c->n * c->d * 8));
-    HIP_TRY(launch_scale_inputs(c->stream, c->Xs.as<double>(), c->ard_rdev.as<double>(), c->n, c->d, c->Xsz.as<double>()));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    box_scale(c->boxXs, c->ard_r, c->boxZs);
-    return GPMI_OK;
-}
-
-// L^T x = b on the resident fused factor (a5): the first call after a factorisation inverts the 128 x 128 diagonal
-// blocks into their upper triangles (one launch, all blocks at once), every call then runs one product per block
-hipError_t gpmi::backward_solve_fused(gpmi_ctx* c, double* b, double* xout) {
-    double* A = c->A.as<double>();
-    const int mode = tuning().trsv_vinv;
-    if (!mode) return launch_trsv_lt_fused(c->stream, A, c->ldA, b, xout, c->Np);
-    hipError_t e;
-    if (mode >= 2 && (e = c->vside.ensure((size_t)c->Np * 128 * 8)) != hipSuccess) return e;
-    if (!c->res.have_vinv || (mode >= 2 && !c->res.have_vside)) {
-        e = launch_vinv128(c->stream, A, c->ldA, c->Np, mode >= 2 ? c->vside.as<double>() : nullptr);
-        if (e != hipSuccess) return e;
-        c->res.block_inverses_made(mode >= 2);
-    }
-    if (mode >= 2) {
-        if ((e = c->flag.ensure(64)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(c->flag.p, 0, 64, c->stream)) != hipSuccess) return e;
-        return launch_trsv_lt_chain(c->stream, A, c->ldA, c->vside.as<double>(), b, xout, c->Np, c->flag.as<int>());
-    }
-    return launch_trsv_lt_vinv(c->stream, A, c->ldA, b, xout, c->Np);
-}
-
-hipError_t gpmi::backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out) {
-    // padded tail of m is zero (identity padding), so the padded system stays consistent
-    hipError_t e = hipMemcpyAsync(x2, c->m_row(), (size_t)c->Np * 8, hipMemcpyDeviceToDevice, c->stream);
-    if (e != hipSuccess) return e;
-    *x_out = c->res.factor_fused ? x2 + c->Np : x2;
-    if (c->res.factor_fused) return backward_solve_fused(c, x2, x2 + c->Np);
-    return launch_trsv_lt(c->stream, c->A.as<double>(), c->ldA, x2, c->Np);
-}
-
-extern "C" {
-
 int gpmi_get_alpha(gpmi_ctx* c, double* alpha_out) {
     if (!c || !alpha_out) return fail_arg("gpmi_get_alpha: null argument");
-    if (!c->res.regression()) return fail_arg("gpmi_get_alpha: no factorisation resident");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
-    hipStream_t s = c->stream;
-    c->timers_reset({GPMI_T_ALPHA});
-    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
-    double* x = c->vec.as<double>();
-    size_t sp = c->span_begin(GPMI_T_ALPHA);
-    HIP_TRY(backward_solve_resident(c, x, &x));
-    c->span_end(sp);
-    HIP_TRY(hipMemcpyAsync(alpha_out, x, (size_t)c->N * 8, hipMemcpyDeviceToHost, s));
-    int gave_up = 0;
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_get_alpha: the single-launch backward solve gave up waiting for a block");
-    return GPMI_OK;
+    return alpha_impl(c, alpha_out);
 }
 
 int gpmi_set_test(gpmi_ctx* c, const double* Xs, int64_t n) {
@@ -488,41 +439,10 @@ int gpmi_set_test(gpmi_ctx* c, const double* Xs, int64_t n) {
 
 int gpmi_predict_resident(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
     if (!c) return fail_arg("gpmi_predict: null context");
-    if (!c->res.regression()) return fail_arg("gpmi_predict: no factorisation resident (call gpmi_factorize)");
-    if (!c->res.have_test) return fail_arg("gpmi_predict: no test set (call gpmi_set_test)");
     HIP_TRY(hipSetDevice(c->device));
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
-    hipStream_t s = c->stream;
-    c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
-    c->res.drop_v();
-    c->ldV = c->Np + c->ld_pad;
-    HIP_TRY(c->V.ensure((size_t)c->np_ * c->ldV * 8));
-    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
-    double* V = c->V.as<double>();
-
-    size_t sp = c->span_begin(GPMI_T_KS);
-    const RbfArgs r = rbf_test_train(c, V, c->ldV);
-    HIP_TRY(launch_rbf(s, r));
-    c->span_end(sp);
-
-    sp = c->span_begin(GPMI_T_SOLVE_V);
-    HIP_TRY(solve_sweep(c, V, c->ldV, c->np_));
-    c->span_end(sp);
-
-    sp = c->span_begin(GPMI_T_MEANVAR);
-    double* dot = c->vec.as<double>();
-    double* sq = dot + c->np_;
-    HIP_TRY(launch_row_dots(s, V, c->ldV, c->np_, c->Np, c->m_row(), dot, sq));
-    c->span_end(sp);
-
-    std::vector<double> h(2 * (size_t)c->np_);
-    HIP_TRY(hipMemcpyAsync(h.data(), dot, h.size() * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    c->res.v_computed();
-    meanvar_to_host(c, h, mu, out2, want_sd);
-    return GPMI_OK;
+    return predict_resident_impl(c, mu, out2, want_sd);
 }
 
 // prediction() in one pass (a11 = a1 .. a8 for a training AND a test set known up front, GP_regression.py:109-156): the
@@ -562,383 +482,59 @@ int gpmi_predict(gpmi_ctx* c, const double* Xs, int64_t n, double* mu, double* o
     return gpmi_predict_resident(c, mu, out2, want_sd);
 }
 
-// The front of both LML gradients and of the leave-one-out calls, inside a timer span of the caller's slot that it opens:
-// alpha = L^-T m (a5; the caller reads the backward solve's give-up word), U = L^-T by the TRSM sweep on the identity
-// and -- want_kn -- Kn = -U U^T on the lower tiles (row block i needs the columns from its first row on only).
-static int grad_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span) {
-    hipStream_t s = c->stream;
-    const int64_t Np = c->Np, ld = c->ldA;
-    HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
-    if (want_kn) HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
-    HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
-    *span = c->span_begin(slot);
-    // alpha = L^-T m (a5)
-    HIP_TRY(backward_solve_resident(c, c->vec.as<double>(), alpha_out));
-    // U = I * L^-T
-    double* U = c->U.as<double>();
-    HIP_TRY(launch_fill_rows(s, U, ld, Np, Np, 0.0));
-    HIP_TRY(launch_set_identity_diag(s, U, ld, Np));
-    HIP_TRY(solve_sweep(c, U, ld, Np, true));
-    if (!want_kn) return GPMI_OK;
-    // Kn = -U U^T, lower tiles: row block i needs columns >= its first row only
-    double* Kn = c->Kn.as<double>();
-    HIP_TRY(launch_fill_rows(s, Kn, ld, Np, Np, 0.0));
-    const int64_t NB = c->block(Np);
-    for (int64_t r0 = 0; r0 < Np; r0 += NB) {
-        const int64_t nb = std::min<int64_t>(NB, Np - r0);
-        GemmArgs g;
-        g.C = Kn + r0 * ld; g.A = U + r0 * ld + r0; g.B = U + r0;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = nb; g.N = r0 + nb; g.K = Np - r0;
-        g.mode = 0; g.lower = 1; g.diag_off = r0;
-        HIP_TRY(launch_gemm_nt(s, g));
-    }
-    return GPMI_OK;
-}
-
-// f2 -- gradient of the log marginal likelihood at the resident factorisation:
-// 0.5 * tr((alpha alpha^T - K_y^-1) dK/dtheta)  (tune_hyperparms_regression.py:43-57; the reference
-// builds K_y^-1 = inv(L.T) inv(L) at :144 and two N x N products).  Here: U = L^-T by the TRSM
-// sweep on the identity (N^3/3), -K_y^-1 = -U U^T by one MFMA GEMM per row block over the
-// non-zero column range (N^3/3), then one fused pass for the trace (grad.hip).
+// Regression behind its fit (regress.hip): the gradient and leave-one-out calls solve with the kind of leaves that produced
+// the resident factor; the posterior-sample factor is a factorisation of its own and takes the context's options
 int gpmi_lml_grad(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     if (!c || !d_ell || !d_sigma) return fail_arg("gpmi_lml_grad: null argument");
-    if (!c->res.regression()) return fail_arg("gpmi_lml_grad: no factorisation resident (call gpmi_factorize)");
-    if (c->kind != 0) return fail_arg("gpmi_lml_grad: squared-exponential kernel only (tune_hyperparms_regression.py:54)");
     HIP_TRY(hipSetDevice(c->device));
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
-    hipStream_t s = c->stream;
-    const int64_t ld = c->ldA;
-    c->timers_reset({GPMI_T_GRAD});
-    double* alpha = nullptr;
-    size_t sp = 0;
-    int rc = grad_front(c, GPMI_T_GRAD, true, &alpha, &sp);
-    if (rc) return rc;
-    double* Kn = c->Kn.as<double>();
-    GradArgs a;
-    a.A = a.B = c->x_train(); a.nA = a.nB = c->N; a.d = c->d;
-    a.row0 = 0; a.nrows = c->N;
-    a.alpha_r = a.alpha_c = alpha;
-    a.Kinv = Kn; a.ld = ld; a.kinv_sign = -1.0;
-    a.coef = c->coef; a.sig2 = c->sig2; a.two_sigma = 2 * c->sigma;
-    a.inv_l3 = 1.0 / (c->ell * c->ell * c->ell);
-    a.tri = 1;
-    const int64_t nblk = grad_trace_blocks(a);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * 16));
-    a.partial = c->gpart.as<double>();
-    HIP_TRY(launch_grad_trace(s, a));
-    c->span_end(sp);
-    std::vector<double> part((size_t)nblk * 2);
-    HIP_TRY(hipMemcpyAsync(part.data(), a.partial, part.size() * 8, hipMemcpyDeviceToHost, s));
-    int gave_up = 0;      // the one-launch backward solve's "a poll gave up" word, as gpmi_get_alpha reads it
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_lml_grad: the single-launch backward solve gave up waiting for a block");
-    double sl = 0.0, ss = 0.0;
-    for (int64_t b = 0; b < nblk; ++b) { sl += part[2 * b]; ss += part[2 * b + 1]; }   // fixed order
-    *d_ell = .5 * sl;
-    *d_sigma = .5 * ss;
-    return GPMI_OK;
+    return lml_grad_impl(c, d_ell, d_sigma);
 }
 
-// The gradient with one lengthscale per input dimension, the output scale and the noise: d + 3 traces of the same
-// W = alpha alpha^T - K_y^-1 in one fused pass (grad.hip, the ARD kernel).  alpha, U and -K_y^-1 are formed exactly as in
-// gpmi_lml_grad; the per-block partials are summed on the device in a fixed order (at N = 65536 they are tens of MB).
 int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise) {
     if (!c) return fail_arg("gpmi_lml_grad_ard: null context");
-    if (!c->res.regression()) return fail_arg("gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)");
-    if (c->kind != 0) return fail_arg("gpmi_lml_grad_ard: squared-exponential kernel only");
     HIP_TRY(hipSetDevice(c->device));
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
-    hipStream_t s = c->stream;
-    const int64_t ld = c->ldA;
-    c->timers_reset({GPMI_T_GRAD});
-    double* alpha = nullptr;
-    size_t sp = 0;
-    int rc = grad_front(c, GPMI_T_GRAD, true, &alpha, &sp);
-    if (rc) return rc;
-    double* Kn = c->Kn.as<double>();
-    GradArdArgs a;
-    a.Z = c->x_train(); a.n = c->N; a.d = c->d;
-    a.alpha = alpha; a.Kn = Kn; a.ld = ld; a.coef = c->coef;
-    const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
-    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
-    a.partial = c->gpart.as<double>();
-    a.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_ard(s, a));
-    c->span_end(sp);
-    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
-    HIP_TRY(hipMemcpyAsync(sums.data(), a.sums, sums.size() * 8, hipMemcpyDeviceToHost, s));
-    int gave_up = 0;
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_lml_grad_ard: the single-launch backward solve gave up waiting for a block");
-    // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums
-    const double l2 = c->ell * c->ell;
-    if (d_r)
-        for (int64_t k = 0; k < c->d; ++k) {
-            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
-            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
-        }
-    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
-    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
-    if (d_noise) *d_noise = .5 * sums[(size_t)w + 2];
-    return GPMI_OK;
+    return lml_grad_ard_impl(c, d_r, d_ell, d_sigma, d_noise);
 }
 
-// Leave-one-out cross-validation at the resident factorisation (GPML section 5.4.2, eqs. 5.10-5.12): with alpha =
-// K_y^-1 y and kappa_i = [K_y^-1]_ii the prediction of y_i from the other N - 1 points is N(y_i - alpha_i / kappa_i,
-// 1 / kappa_i).  alpha and U = L^-T as in gpmi_lml_grad; kappa_i is the squared norm of row i of U (K_y^-1 = U U^T), so
-// the N^3/3 product -U U^T of the gradients is not needed.  Reads L, m and y only: every kernel kind.
 int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
     if (!c) return fail_arg("gpmi_loo: null context");
-    if (!c->res.regression()) return fail_arg("gpmi_loo: no regression factorisation resident (call gpmi_factorize)");
     HIP_TRY(hipSetDevice(c->device));
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
-    hipStream_t s = c->stream;
-    const int64_t N = c->N, Np = c->Np, ld = c->ldA;
-    c->timers_reset({GPMI_T_LOO});
-    HIP_TRY(c->loov.ensure((size_t)(4 * Np + 8) * 8));
-    double* kappa = c->loov.as<double>();
-    double *dmu = kappa + Np, *dvar = dmu + Np, *dlogp = dvar + Np, *dsum = dlogp + Np;
-    double* alpha = nullptr;
-    size_t sp = 0;
-    int rc = grad_front(c, GPMI_T_LOO, false, &alpha, &sp);
-    if (rc) return rc;
-    HIP_TRY(launch_loo_kappa(s, c->U.as<double>(), ld, N, kappa));
-    HIP_TRY(launch_loo_points(s, c->y.as<double>(), alpha, kappa, N, dmu, dvar, dlogp, dsum));
-    c->span_end(sp);
-    if (mu) HIP_TRY(hipMemcpyAsync(mu, dmu, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    if (var) HIP_TRY(hipMemcpyAsync(var, dvar, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    if (logp) HIP_TRY(hipMemcpyAsync(logp, dlogp, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    double sum = 0.0;
-    HIP_TRY(hipMemcpyAsync(&sum, dsum, 8, hipMemcpyDeviceToHost, s));
-    int gave_up = 0;      // the one-launch backward solve's "a poll gave up" word, as gpmi_get_alpha reads it
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_loo: the single-launch backward solve gave up waiting for a block");
-    if (loo) *loo = sum;
-    return GPMI_OK;
+    return loo_impl(c, mu, var, logp, loo);
 }
 
-// The derivatives of the leave-one-out log probability (GPML eq. 5.13) w.r.t. l, sigma and the noise variance:
-//   sum_i (alpha_i r_i - .5 (1 + alpha_i^2 / kappa_i) s_i) / kappa_i,   r = Z alpha,  s_i = [Z K_y^-1]_ii,  Z = K_y^-1 dK_y
-// alpha, U and Kn = -K_y^-1 as in gpmi_lml_grad; kappa from U as in gpmi_loo; Kn mirrored into a full matrix; D = K o sq
-// (dK/dl = D / l^3) built in full into U's buffer, which is dead by then; one pass over the rows of D for t = D alpha and
-// one over the rows of Kn for c_i = sum_a Kn_ia^2, Kn alpha and Kn t; then K_y^-1 D one row block at a time (the routed
-// GEMM into an NB x ld workspace, 2 N^3 flops in all) with s_i read off each block by a row dot with Kn -- the product is
-// never stored whole.  sigma and the noise need no N^3 product (dK_y = 2 (K_y - noise I) / sigma and I).
 int gpmi_loo_grad(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) {
     if (!c) return fail_arg("gpmi_loo_grad: null context");
-    if (!c->res.regression()) return fail_arg("gpmi_loo_grad: no regression factorisation resident (call gpmi_factorize)");
-    if (c->kind != 0) return fail_arg("gpmi_loo_grad: squared-exponential kernel only");
     HIP_TRY(hipSetDevice(c->device));
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
-    hipStream_t s = c->stream;
-    const int64_t N = c->N, Np = c->Np, ld = c->ldA;
-    const int64_t NB = std::min<int64_t>(c->block(Np), Np);
-    c->timers_reset({GPMI_T_LOO});
-    HIP_TRY(c->loov.ensure((size_t)(6 * Np + 8) * 8));
-    HIP_TRY(c->loow.ensure((size_t)NB * ld * 8));
-    double* kappa = c->loov.as<double>();
-    double *cn = kappa + Np, *qn = cn + Np, *un = qn + Np, *t = un + Np, *sn = t + Np, *sums = sn + Np;
-    double* alpha = nullptr;
-    size_t sp = 0;
-    int rc = grad_front(c, GPMI_T_LOO, true, &alpha, &sp);
-    if (rc) return rc;
-    double *D = c->U.as<double>(), *Kn = c->Kn.as<double>(), *W = c->loow.as<double>();
-    HIP_TRY(launch_loo_kappa(s, D, ld, N, kappa));               // U is still L^-T here
-    HIP_TRY(launch_mirror_lower(s, Kn, ld, Np));
-    HIP_TRY(launch_loo_dmat(s, c->x_train(), N, c->d, c->coef, c->sig2, D, ld, Np));
-    HIP_TRY(launch_row_pass(s, D, ld, N, alpha, nullptr, nullptr, t, nullptr));
-    HIP_TRY(launch_row_pass(s, Kn, ld, N, alpha, t, cn, qn, un));
-    for (int64_t r0 = 0; r0 < N; r0 += NB) {                     // a row block of padding only has nothing to give
-        const int64_t nb = std::min<int64_t>(NB, Np - r0);
-        HIP_TRY(launch_fill_rows(s, W, ld, nb, Np, 0.0));
-        GemmArgs g;                                              // W = -Kn[r0 .. r0 + nb) D^T = (K_y^-1 D) rows; D is symmetric
-        g.C = W; g.A = Kn + r0 * ld; g.B = D;
-        g.ldc = g.lda = g.ldb = ld;
-        g.M = nb; g.N = Np; g.K = Np;
-        g.mode = 0; g.lower = 0; g.diag_off = 0;
-        HIP_TRY(launch_gemm_nt(s, g));
-        HIP_TRY(launch_row_dot2(s, W, ld, Kn + r0 * ld, ld, std::min<int64_t>(nb, N - r0), N, sn + r0));
-    }
-    LooGradArgs a;
-    a.alpha = alpha; a.kappa = kappa; a.cn = cn; a.qn = qn; a.un = un; a.sn = sn;
-    a.n = N; a.noise = c->noise; a.out3 = sums;
-    HIP_TRY(launch_loo_grad_sums(s, a));
-    c->span_end(sp);
-    double h[3] = {0.0, 0.0, 0.0};
-    HIP_TRY(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, s));
-    int gave_up = 0;
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (gave_up) return fail_runtime(hipErrorUnknown, "gpmi_loo_grad: the single-launch backward solve gave up waiting for a block");
-    if (d_ell) *d_ell = h[0] / (c->ell * c->ell * c->ell);
-    if (d_sigma) *d_sigma = 2.0 / c->sigma * h[1];
-    if (d_noise) *d_noise = h[2];
-    return GPMI_OK;
+    return loo_grad_impl(c, d_ell, d_sigma, d_noise);
 }
 
-// The same trace from caller-supplied alpha and K_y^-1 (host, N x N row-major): the arguments the
-// reference's gradient_ascent(a, b, sigma, l, alpha, K_y) receives (tune_hyperparms_regression.py:31).
 int gpmi_grad_trace(gpmi_ctx* c, const double* a_in, const double* b_in, int64_t N, int64_t d, double sigma,
                     double ell, const double* alpha_in, const double* Kinv_in, double* d_ell, double* d_sigma) {
     if (!c || !a_in || !b_in || !alpha_in || !Kinv_in || !d_ell || !d_sigma) return fail_arg("gpmi_grad_trace: null argument");
-    if (N <= 0 || d <= 0) return fail_arg("gpmi_grad_trace: N and d must be positive");
-    if (!(ell != 0.0)) return fail_arg("gpmi_grad_trace: ell must be non-zero");
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    DevBuf da, db, dal, dk, dp;
-    const int64_t chunk = std::max<int64_t>(TILE, std::min<int64_t>(round_up(N, TILE), ((int64_t)1 << 30) / (N * 8) / TILE * TILE));
-    int rc = GPMI_OK;
-    hipError_t e = hipSuccess;
-    double sl = 0.0, ss = 0.0;
-    do {
-        if ((e = da.ensure((size_t)N * d * 8)) != hipSuccess || (e = db.ensure((size_t)N * d * 8)) != hipSuccess ||
-            (e = dal.ensure((size_t)N * 8)) != hipSuccess || (e = dk.ensure((size_t)chunk * N * 8)) != hipSuccess) {
-            rc = fail_runtime(e, "hipMalloc"); break;
-        }
-        if ((e = hipMemcpyAsync(da.p, a_in, (size_t)N * d * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-            (e = hipMemcpyAsync(db.p, b_in, (size_t)N * d * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-            (e = hipMemcpyAsync(dal.p, alpha_in, (size_t)N * 8, hipMemcpyHostToDevice, s)) != hipSuccess) {
-            rc = fail_runtime(e, "hipMemcpy H2D"); break;
-        }
-        for (int64_t r0 = 0; r0 < N && rc == GPMI_OK; r0 += chunk) {
-            const int64_t rows = std::min(chunk, N - r0);
-            if ((e = hipMemcpyAsync(dk.p, Kinv_in + r0 * N, (size_t)rows * N * 8, hipMemcpyHostToDevice, s)) != hipSuccess) {
-                rc = fail_runtime(e, "hipMemcpy H2D"); break;
-            }
-            GradArgs g;
-            g.A = da.as<double>(); g.B = db.as<double>(); g.nA = g.nB = N; g.d = d;
-            g.row0 = r0; g.nrows = rows;
-            g.alpha_r = g.alpha_c = dal.as<double>();
-            g.Kinv = dk.as<double>(); g.ld = N; g.kinv_sign = 1.0;
-            g.coef = -.5 * (1 / (ell * ell)); g.sig2 = sigma * sigma; g.two_sigma = 2 * sigma;
-            g.inv_l3 = 1.0 / (ell * ell * ell);
-            g.tri = 0;
-            const int64_t nblk = grad_trace_blocks(g);
-            if ((e = dp.ensure((size_t)nblk * 16)) != hipSuccess) { rc = fail_runtime(e, "hipMalloc"); break; }
-            g.partial = dp.as<double>();
-            std::vector<double> part((size_t)nblk * 2);
-            if ((e = launch_grad_trace(s, g)) != hipSuccess ||
-                (e = hipMemcpyAsync(part.data(), g.partial, part.size() * 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                (e = hipStreamSynchronize(s)) != hipSuccess) {
-                rc = fail_runtime(e, "gradient trace"); break;
-            }
-            for (int64_t b = 0; b < nblk; ++b) { sl += part[2 * b]; ss += part[2 * b + 1]; }
-        }
-    } while (0);
-    (void)hipStreamSynchronize(s);
-    da.release(); db.release(); dal.release(); dk.release(); dp.release();
-    if (rc == GPMI_OK) { *d_ell = .5 * sl; *d_sigma = .5 * ss; }
-    return rc;
-}
-
-// the posterior-sample factor on the device: where cholesky(K_ss + jitter I - v^T v) of the resident test set sits (factor, ld)
-// -- behind L when it rode through the augmented factorisation (gpmi_fit_predict_sample_resident), else formed now in P
-// (K_ss build, v^T v by one MFMA SYRK, the same Cholesky) unless P already holds it for this jitter
-static int post_factor_device(gpmi_ctx* c, double jitter, const double** factor, int64_t* ld, int64_t* bad_pivot) {
-    if (!c->res.have_v) return fail_arg("gpmi_post_chol: run gpmi_predict first");
-    hipStream_t s = c->stream;
-    const int64_t np_ = c->np_, n = c->n;
-    if (bad_pivot) *bad_pivot = 0;
-    if (c->res.post_rides(jitter)) {
-        *factor = c->A.as<double>() + c->Np * c->ldA + c->Np;
-        *ld = c->ldA;
-        return GPMI_OK;
-    }
-    if (c->res.post_cached(jitter)) {
-        *factor = c->P.as<double>();
-        *ld = c->ldP;
-        return GPMI_OK;
-    }
-    c->res.drop_post_in_P();
-    c->timers_reset({GPMI_T_POSTCHOL});
-    c->ldP = np_ + 32;
-    HIP_TRY(c->P.ensure((size_t)np_ * c->ldP * 8));
-    double* P = c->P.as<double>();
-    const int64_t big = std::numeric_limits<int64_t>::max();
-    HIP_TRY(hipMemcpyAsync(c->info.p, &big, sizeof big, hipMemcpyHostToDevice, s));
-    size_t sp = c->span_begin(GPMI_T_POSTCHOL);
-    // K_ss + jitter*I, lower tiles (GP_regression.py:128,154)
-    const RbfArgs r = rbf_sym(c, c->x_test(), n, c->box_test(), jitter, np_, P, c->ldP);
-    HIP_TRY(launch_rbf(s, r));
-    GemmArgs g;  // P -= v^T v  (rows of V are the columns of v)
-    g.C = P; g.A = g.B = c->v_rows();
-    g.ldc = c->ldP; g.lda = g.ldb = c->ldV;
-    g.M = g.N = np_; g.K = c->Np; g.mode = 0; g.lower = 1; g.diag_off = 0;
-    HIP_TRY(launch_gemm_nt(s, g));
-    HIP_TRY(cholesky_inplace(c, P, c->ldP, np_, np_, c->info.as<int64_t>(), false));
-    c->span_end(sp);
-    int64_t info;
-    HIP_TRY(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    c->timers_collect();
-    if (info != big && info < n) {
-        if (bad_pivot) *bad_pivot = info + 1;
-        g_err = "Matrix is not positive definite";
-        return GPMI_ERR_NOT_PD;
-    }
-    c->res.post_cached_in_P(jitter);
-    *factor = P;
-    *ld = c->ldP;
-    return GPMI_OK;
+    return grad_trace_impl(c, a_in, b_in, N, d, sigma, ell, alpha_in, Kinv_in, d_ell, d_sigma);
 }
 
 int gpmi_post_chol(gpmi_ctx* c, double jitter, double* L_out, int64_t* bad_pivot) {
     if (!c || !L_out) return fail_arg("gpmi_post_chol: null argument");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
-    const double* F = nullptr;
-    int64_t ld = 0;
-    int rc = post_factor_device(c, jitter, &F, &ld, bad_pivot);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const int64_t n = c->n;
-    HIP_TRY(c->dense.ensure((size_t)n * n * 8));
-    HIP_TRY(launch_extract(s, F, ld, 0, n, 0, n, c->dense.as<double>(), 1));
-    HIP_TRY(hipMemcpyAsync(L_out, c->dense.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return GPMI_OK;
+    return post_chol_impl(c, jitter, L_out, bad_pivot);
 }
 
-// L_ @ Z for the posterior samples f_post = mu + L_ @ normals (GP_regression.py:155) without bringing L_ to the host: Z
-// (n x num_fun row-major, the caller's normals -- drawn on the host so that np.random's order is the reference's) goes up,
-// the product comes down.  The factor is the one gpmi_post_chol(jitter) would return.
 int gpmi_post_sample(gpmi_ctx* c, double jitter, const double* Z, int64_t num_fun, double* LZ_out, int64_t* bad_pivot) {
     if (!c || !Z || !LZ_out) return fail_arg("gpmi_post_sample: null argument");
-    if (num_fun <= 0 || num_fun > (1 << 20)) return fail_arg("gpmi_post_sample: num_fun must be in 1 .. 2^20");
     HIP_TRY(hipSetDevice(c->device));
     TuneScope tune_scope(&c->tune);
-    const double* F = nullptr;
-    int64_t ld = 0;
-    int rc = post_factor_device(c, jitter, &F, &ld, bad_pivot);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    const int64_t n = c->n;
-    const size_t bytes = (size_t)n * (size_t)num_fun * 8;
-    HIP_TRY(c->dense.ensure(2 * bytes));
-    double* Zd = c->dense.as<double>();
-    double* Od = Zd + (size_t)n * (size_t)num_fun;
-    HIP_TRY(hipMemcpyAsync(Zd, Z, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_tri_mul(s, F, ld, Zd, n, num_fun, Od));
-    HIP_TRY(hipMemcpyAsync(LZ_out, Od, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return GPMI_OK;
+    return post_sample_impl(c, jitter, Z, num_fun, LZ_out, bad_pivot);
 }
 
 // Lane l of a batch: its own context (streams, A, workspaces) on the same device, with the parent's

@@ -260,6 +260,10 @@ hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri 
 // the same sweep through any resident lower factor (ncols x ncols, leading dimension ld), not only the one in c->A
 hipError_t solve_sweep_factor(gpmi_ctx* c, const double* L, int64_t ld, int64_t ncols, double* V, int64_t ldv, int64_t m,
                               bool tri = false);
+// V = F^-T (upper triangular, n x n) for a resident lower factor F by that sweep on the identity, and Out = -V V^T on the
+// lower tiles for such a V, one launch per row block of c->block(n) rows
+hipError_t inverse_transposed(gpmi_ctx* c, const double* F, int64_t ldf, int64_t n, double* V, int64_t ldv);
+hipError_t neg_gram_lower(gpmi_ctx* c, const double* V, double* Out, int64_t ld, int64_t n);
 // The kernel-matrix launches of a context, ready for launch_rbf.  rbf_cross: rows row0 .. row0 + nrows of K(A, B) for point
 // sets of nA and nB points with boxes ba and bb, ncols columns, nothing on the diagonal; the delta term of the composite
 // kernel counts as on a square matrix only for the test set against a training set of the same size.  rbf_sym: the lower
@@ -281,11 +285,23 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
 int ard_rescale_train(gpmi_ctx* c);
 int ard_rescale_test(gpmi_ctx* c);
 void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, double* out2, int want_sd);
-// gpmi_api.hip: L^T x = b on the resident fused factor (a5; the first call after a factorisation inverts its diagonal blocks)
+// regress.hip: L^T x = b on the resident fused factor (a5; the first call after a factorisation inverts its diagonal blocks)
 hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout);
 // x = L^-T m for the m of the y row, through the fused solve or the plain one as the resident factor asks: x2 holds 2 Np
-// doubles, *x_out says where in it the solution lies
+// doubles, *x_out says where in it the solution lies; fail_gave_up: the status of a one-launch solve whose give-up word is set
 hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out);
+int fail_gave_up(const char* api);
+// regress.hip: the regression calls of include/gpmi.h on the resident factorisation, behind the shims' pointer checks
+int alpha_impl(gpmi_ctx* c, double* alpha_out);
+int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
+int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma);
+int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
+int loo_impl(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo);
+int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise);
+int grad_trace_impl(gpmi_ctx* c, const double* a_in, const double* b_in, int64_t N, int64_t d, double sigma, double ell,
+                    const double* alpha_in, const double* Kinv_in, double* d_ell, double* d_sigma);
+int post_chol_impl(gpmi_ctx* c, double jitter, double* L_out, int64_t* bad_pivot);
+int post_sample_impl(gpmi_ctx* c, double jitter, const double* Z, int64_t num_fun, double* LZ_out, int64_t* bad_pivot);
 // the context's options with the panel kind of the resident factor: solve with the kind of leaves that produced it
 inline Tuning resident_tuning(const gpmi_ctx* c) {
     Tuning tn = c->tune;

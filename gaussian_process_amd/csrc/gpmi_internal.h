@@ -67,9 +67,9 @@ struct GemmArgs {
     const double* B;
     int64_t ldc, lda, ldb;
     int64_t M, N, K;
-    int mode;
-    int lower;
-    int64_t diag_off;
+    int mode = 0;
+    int lower = 0;
+    int64_t diag_off = 0;
     // optional: row_ncols[ti / row_block_tiles] = number of leading columns of C that
     // the 128-row tile band ti updates (row-block cyclic storage: a rank's stacked
     // row blocks reach different distances to the right); device pointer or null
@@ -86,6 +86,22 @@ struct GemmArgs {
     const int64_t* b_block_off = nullptr;
     int64_t b_block_rows = 0;
 };
+// C -= A B^T over the whole rectangle; a launch with a row map, a block table or a role adds its fields to this
+inline GemmArgs gemm_minus(double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M,
+                           int64_t N, int64_t K) {
+    GemmArgs g;
+    g.C = C; g.A = A; g.B = B;
+    g.ldc = ldc; g.lda = lda; g.ldb = ldb;
+    g.M = M; g.N = N; g.K = K;
+    return g;
+}
+// ... on the tiles that reach {col <= row + diag_off} only
+inline GemmArgs gemm_minus_lower(double* C, int64_t ldc, const double* A, int64_t lda, const double* B, int64_t ldb,
+                                 int64_t M, int64_t N, int64_t K, int64_t diag_off) {
+    GemmArgs g = gemm_minus(C, ldc, A, lda, B, ldb, M, N, K);
+    g.lower = 1; g.diag_off = diag_off;
+    return g;
+}
 // The route of a launch (gpmi_route.h: gemm_route; a launch that wants a resident form creates the device's counter
 // pool here), and the launch of a route -- for a caller that accounts by the kernel family it reaches.
 GemmRoute gemm_nt_route(const GemmArgs& a);

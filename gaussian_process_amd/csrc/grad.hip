@@ -283,7 +283,7 @@ __global__ void set_identity_kernel(double* V, int64_t ld, int64_t n) {
 }
 
 // ---- leave-one-out cross-validation (GPML section 5.4.2) ------------------------------------------------------------
-// Small N^2 passes around the N^3 products of gpmi_loo / gpmi_loo_grad (gpmi_api.hip).  The row kernels give one wave a
+// Small N^2 passes around the N^3 products of gpmi_loo / gpmi_loo_grad (regress.hip).  The row kernels give one wave a
 // row: lane t reads the column pairs 2t, 2t + 128, ... with 16-byte loads (a wave reads 1 KiB per instruction) and adds
 // them in that order, the 64 lanes meet in a butterfly -- the same order every run.  They read rows and columns < n
 // only: whatever the identity padding holds contributes nothing.

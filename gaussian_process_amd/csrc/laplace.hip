@@ -280,7 +280,7 @@ int newton_readback(gpmi_ctx* c, const double* psi_part, int64_t nblk, bool chai
     c->timers_collect();
     const std::string who = std::string(api) + ": ";
     if (h[1] != (double)NO_BAD_PIVOT) { g_err = who + pivot_text; return GPMI_ERR_NOT_PD; }
-    if (h[2] != 0.0) return fail_runtime(hipErrorUnknown, (who + "the single-launch backward solve gave up waiting for a block").c_str());
+    if (h[2] != 0.0) return fail_gave_up(api);
     if (!std::isfinite(h[0])) return fail_arg((who + "the objective is not finite").c_str());
     return GPMI_OK;
 }

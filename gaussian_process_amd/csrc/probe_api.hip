@@ -90,9 +90,8 @@ int gpmi_probe_gemm(gpmi_ctx* c, int64_t M, int64_t N, int64_t K, int lower, int
             (void)launch_fill_rows(s, A.as<double>(), ldk, M, K, 0.001);
             (void)launch_fill_rows(s, B.as<double>(), ldk, N, K, -0.002);
         }
-        GemmArgs g;
-        g.C = C.as<double>(); g.A = A.as<double>(); g.B = B.as<double>();
-        g.ldc = ldc; g.lda = g.ldb = ldk; g.M = M; g.N = N; g.K = K; g.mode = 0; g.lower = lower; g.diag_off = 0;
+        GemmArgs g = gemm_minus(C.as<double>(), ldc, A.as<double>(), ldk, B.as<double>(), ldk, M, N, K);
+        g.lower = lower;
         DevBuf stamps;
         if (variant & 16) {
             if ((e = stamps.ensure(4096 * 16 * 8)) != hipSuccess) { rc = fail_runtime(e, "hipMalloc"); break; }

@@ -539,18 +539,7 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
             hipLaunchKernelGGL(softmax_seed_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, V, ld, Np, sk);
             HIP_TRY(hipGetLastError());
             HIP_TRY(solve_sweep(c, V, ld, Np, true));
-            double* Ek = nE + (int64_t)k * msize;
-            HIP_TRY(launch_fill_rows(st, Ek, ld, Np, Np, 0.0));
-            const int64_t NB = c->block(Np);
-            for (int64_t r0 = 0; r0 < Np; r0 += NB) {                 // row block r0 of V is zero left of column r0
-                const int64_t nb = std::min<int64_t>(NB, Np - r0);
-                GemmArgs g;
-                g.C = Ek + r0 * ld; g.A = V + r0 * ld + r0; g.B = V + r0;
-                g.ldc = g.lda = g.ldb = ld;
-                g.M = nb; g.N = r0 + nb; g.K = Np - r0;
-                g.mode = 0; g.lower = 1; g.diag_off = r0;
-                HIP_TRY(launch_gemm_nt(st, g));
-            }
+            HIP_TRY(neg_gram_lower(c, V, nE + (int64_t)k * msize, ld, Np));
         }
         if (!last) {                                                  // 4. c_c = E_c (K b_c), sum_c c_c rides with M
             kx.x = v.b;
@@ -642,12 +631,7 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_fill_rows(st, Bc, ldV, C * np_, Np, 0.0));
     for (int k = 0; k < C; ++k) {                                     // B_c = R E_c = 0 - R (-E_c)^T
-        GemmArgs g;
-        g.C = Bc + (int64_t)k * np_ * ldV; g.A = R; g.B = nE + (int64_t)k * msize;
-        g.ldc = g.lda = ldV; g.ldb = ld;
-        g.M = np_; g.N = Np; g.K = Np;
-        g.mode = 0; g.lower = 0; g.diag_off = 0;
-        HIP_TRY(launch_gemm_nt(st, g));
+        HIP_TRY(launch_gemm_nt(st, gemm_minus(Bc + (int64_t)k * np_ * ldV, ldV, R, ldV, nE + (int64_t)k * msize, ld, np_, Np, Np)));
     }
     hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np,
                        (const double*)Bc, np_ * ldV, ldV, C, o_dd);   // B_c[i] . R[i]

@@ -692,19 +692,7 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
     auto neg_product = [&](double* C, const double* A, const double* B, int64_t rows) -> hipError_t {
         hipError_t e = hipMemsetAsync(C, 0, (size_t)rows * ldm * 8, st);
         if (e != hipSuccess) return e;
-        GemmArgs g;
-        g.C = C; g.A = A; g.B = B;
-        g.ldc = g.lda = g.ldb = ldm;
-        g.M = rows; g.N = mp; g.K = mp;
-        g.mode = 0; g.lower = 0; g.diag_off = 0;
-        return launch_gemm_nt(st, g);
-    };
-    // V = F^-T (upper triangular) for a resident lower factor F, by the sweep on the identity
-    auto inverse_t = [&](const double* F, double* V) -> hipError_t {
-        hipError_t e = hipMemsetAsync(V, 0, mat, st);
-        if (e != hipSuccess) return e;
-        if ((e = launch_set_identity_diag(st, V, ldm, mp)) != hipSuccess) return e;
-        return solve_sweep_factor(c, F, ldm, mp, V, ldm, mp, true);
+        return launch_gemm_nt(st, gemm_minus(C, ldm, A, ldm, B, ldm, rows, mp, mp));
     };
 
     c->timers_reset({GPMI_T_SPARSE, GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR, GPMI_T_POSTCHOL, GPMI_T_CHOL});
@@ -712,7 +700,7 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
     // ---- the m-sized part: GPMI_T_CHOL
     size_t sp = c->span_begin(GPMI_T_CHOL);
     HIP_TRY(hipMemsetAsync(colF, 0, (size_t)(2 * ncol) * 8, st));
-    HIP_TRY(inverse_t(Bm, G0));                                            // G0 = L_B^-T
+    HIP_TRY(inverse_transposed(c, Bm, ldm, mp, G0, ldm));                                            // G0 = L_B^-T
     HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, cvec, u, nullptr));       // u = L_B^-T c
     HIP_TRY(neg_product(G1, G0, G0, mp));                                  // G1 = -B^-1
     hipLaunchKernelGGL(sparse_grad_scalars_kernel, dim3(1), dim3(256), 0, st, (const double*)G1, ldm, m,
@@ -723,7 +711,7 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
     HIP_TRY(neg_product(G2, G0, G0, mp));                                  // G2 = -B
     hipLaunchKernelGGL(sparse_grad_core_kernel, egrid, dim3(256), 0, st, G2, G1, (const double*)u, ldm, mp, inv_s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(inverse_t(Lm, G0));                                            // G0 = L^-T
+    HIP_TRY(inverse_transposed(c, Lm, ldm, mp, G0, ldm));                                            // G0 = L^-T
     HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, u, p, nullptr));          // p = L^-T u
     HIP_TRY(neg_product(E, G0, G1, mp));
     HIP_TRY(neg_product(G1, E, G0, mp));                                   // G1 = -T
