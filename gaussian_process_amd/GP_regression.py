@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .gp import default_context, split_lengthscale
+from .gp import GPContext, default_context, split_lengthscale
 
 NOISE_VAR = 0.0005      # GP_regression.py:120
 SIGMA_F = 1             # GP_regression.py:121
@@ -33,6 +33,37 @@ def RBF_kernel(a, b, sigma, l):
         a = np.asarray(a, dtype=np.float64) / r
         b = np.asarray(b, dtype=np.float64) / r
     return default_context().rbf(a, b, sigma, l)
+
+
+def matern_kernel(a, b, sigma, l, nu=1.5):
+    """Matern kernel matrix sigma**2 P(t) exp(-t), t = sqrt(2 nu) |a - b| / l, for nu = 0.5, 1.5 or 2.5 (GPML section
+    4.2.1; P = 1, 1 + t, 1 + t + t**2 / 3).  The reference has none; arguments as RBF_kernel.
+
+    :param l: lengthscale (scalar or 1-element array), or a d-vector: one lengthscale per input dimension
+    :return: (N, M) float64 covariance matrix
+    """
+    kind = _matern_kind(nu)
+    l, r = split_lengthscale(l)
+    if r is not None:                   # both inputs scaled on the host, then the isotropic entry with l = 1
+        a = np.asarray(a, dtype=np.float64) / r
+        b = np.asarray(b, dtype=np.float64) / r
+    return default_context().cov(kind, a, b, sigma, l)
+
+
+def _matern_kind(nu):
+    try:
+        return GPContext.MATERN[float(nu)]
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("nu must be 0.5, 1.5 or 2.5, got %r" % (nu,)) from None
+
+
+STATIONARY = ('rbf', 'matern12', 'matern32', 'matern52')     # sigma and l come from the fitting call; l may be a d-vector
+
+
+def _check_stationary(kernel):
+    if kernel not in STATIONARY:
+        raise ValueError("kernel must be one of %s, got %r" % (STATIONARY, kernel))
+    return kernel
 
 
 def dataset_generator(N, n):
@@ -60,9 +91,9 @@ def per_kernel(a, b, parameters):
 
 def _select_kernel(ctx, kernel_choice, parameter, sigma):
     """kernel_choice / parameter conventions of prediction() (GP_regression.py:125-136):
-    'rbf': l; 'lin': the offset c; 'per': the tuple (p, l)."""
-    if kernel_choice == 'rbf':
-        ctx.set_kernel('rbf')
+    'rbf': l; 'lin': the offset c; 'per': the tuple (p, l); 'matern12' / 'matern32' / 'matern52': l, as 'rbf'."""
+    if kernel_choice in STATIONARY:
+        ctx.set_kernel(kernel_choice)
         return sigma, parameter
     if kernel_choice == 'lin':
         ctx.set_kernel('lin', parameter)
@@ -71,7 +102,8 @@ def _select_kernel(ctx, kernel_choice, parameter, sigma):
         p, l = parameter
         ctx.set_kernel('per', p, l)
         return 1.0, 1.0
-    raise ValueError("kernel_choice must be 'rbf', 'lin' or 'per', got %r" % (kernel_choice,))
+    raise ValueError("kernel_choice must be 'rbf', 'lin', 'per', 'matern12', 'matern32' or 'matern52', got %r"
+                     % (kernel_choice,))
 
 
 def _dist_of(n_gpus, dist):
@@ -89,7 +121,8 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
                noise_var=NOISE_VAR, jitter=POST_JITTER, return_lml=False, ctx=None, n_gpus=None, dist=None):
     """GP posterior at the test points, reference GP_regression.py:109-156.
 
-    With kernel_choice 'rbf', l may be a d-vector (d > 1): one lengthscale per input dimension.  A scalar or 1-element l
+    With kernel_choice 'rbf' or a Matern ('matern12', 'matern32', 'matern52'), l may be a d-vector (d > 1): one lengthscale
+    per input dimension.  A scalar or 1-element l
     is the reference's isotropic kernel and clears any per-dimension lengthscales the context carried.
 
     :return: (mu_post (n,), stand_devi (n,), f_post_fun (n, num_fun)); with return_lml=True a
@@ -100,9 +133,11 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
     are drawn on the host from np.random in the reference's order.
     """
     r = None
-    if kernel_choice == 'rbf':
+    if kernel_choice in STATIONARY:
         l, r = split_lengthscale(l)     # a d-vector: one lengthscale per input dimension, common l = 1
     gp = _dist_of(n_gpus, dist)
+    if gp is not None and kernel_choice in STATIONARY[1:]:
+        raise ValueError("the Matern kernels are not available on the partitioned path (n_gpus / dist)")
     if gp is not None and r is not None:
         raise ValueError("per-dimension lengthscales (a vector l) are not available on the partitioned path (n_gpus / dist)")
     if gp is not None:
@@ -142,14 +177,23 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
 
 
 def f_prior(X_test, mu_prior, kernel_choice, kernel_parameter, num_fun, *, ctx=None):
-    """GP prior samples, reference GP_regression.py:71-92 (s = 0.0005, sigma = 1)."""
+    """GP prior samples, reference GP_regression.py:71-92 (s = 0.0005, sigma = 1).  With a Matern kernel_choice the
+    parameter is l, a scalar or a d-vector."""
     ctx = ctx or default_context()
     X_test = np.asarray(X_test, dtype=np.float64)
     num_test = len(X_test)
+    r = None
+    if kernel_choice in STATIONARY[1:]:       # 'rbf' keeps the reference's scalar parameter
+        kernel_parameter, r = split_lengthscale(kernel_parameter)
     try:
         sg, ll = _select_kernel(ctx, kernel_choice, kernel_parameter, SIGMA_F)      # :84-89
-        ctx.fit(X_test, np.zeros(num_test), sg, ll, NOISE_VAR)                      # :90
+        if r is not None:
+            ctx.fit(X_test, np.zeros(num_test), sg, ll, NOISE_VAR, lengthscales=r)
+        else:
+            ctx.fit(X_test, np.zeros(num_test), sg, ll, NOISE_VAR)                  # :90
         B = ctx.factor()
     finally:
         ctx.set_kernel('rbf')
+        if r is not None:
+            ctx.set_lengthscales(None)
     return mu_prior + np.dot(B, np.random.normal(size=(num_test, num_fun)))     # :91

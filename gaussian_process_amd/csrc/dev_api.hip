@@ -37,14 +37,15 @@ int gpmi_dev_rbf_cross(void* stream, const double* Xs_dev, int64_t n, const doub
 
 // covariance parameters of the gpmi_dev_cov_* entry points, as gpmi_set_kernel / gpmi_set_kernel_params take them
 static int dev_cov_args(RbfArgs& r, int kind, const double* params, int nparams, const char* who) {
-    static const int want[4] = {2, 1, 2, 11};
-    if (kind < 0 || kind > 3) return fail_arg("gpmi_dev_cov: kind must be 0 (rbf), 1 (linear), 2 (periodic) or 3 (CO2 composite)");
-    if (!params || nparams != want[kind]) return fail_arg("gpmi_dev_cov: kinds 0 / 1 / 2 / 3 take 2 / 1 / 2 / 11 parameters");
+    static const int want[7] = {2, 1, 2, 11, 2, 2, 2};
+    if (kind < 0 || kind > 6)
+        return fail_arg("gpmi_dev_cov: kind must be 0 (rbf), 1 (linear), 2 (periodic), 3 (CO2 composite) or 4, 5, 6 (Matern)");
+    if (!params || nparams != want[kind]) return fail_arg("gpmi_dev_cov: kinds 0 / 1 / 2 / 3 / 4-6 take 2 / 1 / 2 / 11 / 2 parameters");
     (void)who;
     r.kind = kind;
-    if (kind == 0) {
+    if (cov_stationary(kind)) {
         if (!(params[1] != 0.0)) return fail_arg("gpmi_dev_cov: ell must be non-zero");
-        r.coef = -.5 * (1 / (params[1] * params[1])); r.sig2 = params[0] * params[0];
+        r.coef = cov_coef(kind, params[1]); r.sig2 = params[0] * params[0];
     } else if (kind == 1) {
         r.kp0 = params[0];
     } else if (kind == 2) {

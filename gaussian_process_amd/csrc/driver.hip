@@ -256,7 +256,7 @@ void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, doub
     for (int64_t i = 0; i < c->n; ++i) {
         if (mu) mu[i] = h[i];
         if (out2) {
-            double kss = c->sig2;                          // diag(K_ss) == sigma^2 exactly for the RBF (GP_regression.py:147)
+            double kss = c->sig2;                          // diag(K_ss) == sigma^2 exactly for the RBF (GP_regression.py:147) and the Materns
             if (c->kind == 2) kss = 1.0;                   // periodic: exp(0)
             else if (c->kind == 3) {                       // composite at sqdist 0, square K_ss: every factor is 1
                 const double* th = c->kpv;
@@ -279,11 +279,12 @@ void meanvar_to_host(gpmi_ctx* c, const std::vector<double>& h, double* mu, doub
 int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, double* lml,
                    int64_t* bad_pivot, bool with_test, double* mu, double* out2, int want_sd, bool with_post, double jitter) {
     if (!c->res.have_train) return fail_arg("gpmi_factorize: no training set (call gpmi_set_train)");
-    if (c->kind == 0 && (!(ell != 0.0) || std::isnan(ell) || std::isnan(sigma)))
+    if (cov_stationary(c->kind) && (!(ell != 0.0) || std::isnan(ell) || std::isnan(sigma)))
         return fail_arg("gpmi_factorize: ell must be non-zero and hyper-parameters finite");
     if (std::isnan(noise_var)) return fail_arg("gpmi_factorize: noise_var is NaN");
     if (c->kind == 2 && c->d != 1) return fail_arg("gpmi_factorize: the periodic kernel is 1-D only (GP_regression.py:48)");
-    if (c->kind != 0 && c->ard()) return fail_arg("gpmi_factorize: per-dimension lengthscales need the squared-exponential kernel (kind 0)");
+    if (!cov_stationary(c->kind) && c->ard())
+        return fail_arg("gpmi_factorize: per-dimension lengthscales need the squared-exponential or a Matern kernel (kinds 0, 4, 5, 6)");
     // the test set's rows: inside the panel and update launches (1) or one block column behind on their own stream (2)
     int form = 0;
     if (with_test) {
@@ -308,7 +309,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
                      GPMI_T_TRAIL_LAUNCHES, GPMI_T_TRAIL_FLOPS});
     if (with_test) c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
     c->sig2 = sigma * sigma;
-    c->coef = -.5 * (1 / (ell * ell));      // GP_regression.py:19 evaluation order
+    c->coef = cov_coef(c->kind, ell);       // GP_regression.py:19 evaluation order; a Matern kind: -sqrt(2 nu) / |l|
     c->sigma = sigma; c->ell = ell; c->noise = noise_var;
     double* A = c->A.as<double>();
     const int64_t big = std::numeric_limits<int64_t>::max();

@@ -205,7 +205,8 @@ int gpmi_dev_set_option(const char* name, int64_t value) {
 
 int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
     if (!c) return fail_arg("gpmi_set_kernel: null context");
-    if (kind < 0 || kind > 2) return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear) or 2 (periodic)");
+    if (kind < 0 || kind == 3 || kind > 6)
+        return fail_arg("gpmi_set_kernel: kind must be 0 (rbf), 1 (linear), 2 (periodic) or 4, 5, 6 (Matern nu = 1/2, 3/2, 5/2)");
     if (kind == 2 && (!(p0 != 0.0) || !(p1 != 0.0))) return fail_arg("gpmi_set_kernel: period and lengthscale must be non-zero");
     c->kind = kind; c->kp0 = p0; c->kp1 = p1;
     c->res.drop_fit();
@@ -215,7 +216,7 @@ int gpmi_set_kernel(gpmi_ctx* c, int kind, double p0, double p1) {
 int gpmi_set_kernel_params(gpmi_ctx* c, int kind, const double* params, int nparams) {
     if (!c || !params) return fail_arg("gpmi_set_kernel_params: null argument");
     if (kind != 3) {
-        if (kind < 0 || kind > 2 || nparams != 2) return fail_arg("gpmi_set_kernel_params: kinds 0-2 take 2 parameters");
+        if (kind < 0 || kind > 6 || nparams != 2) return fail_arg("gpmi_set_kernel_params: kinds 0-2 and 4-6 take 2 parameters");
         return gpmi_set_kernel(c, kind, params[0], params[1]);
     }
     if (nparams != 11) return fail_arg("gpmi_set_kernel_params: the CO2 composite kernel takes 11 hyper-parameters (CO2_example.py:86-89)");
@@ -240,7 +241,7 @@ static int cov_impl(gpmi_ctx* c, int kind, const double* a, int64_t N, const dou
 
 int gpmi_cov(gpmi_ctx* c, int kind, const double* a, int64_t N, const double* b, int64_t M, int64_t d,
              double p0, double p1, double* out) {
-    if (kind < 0 || kind > 2) return fail_arg("gpmi_cov: kind must be 0, 1 or 2");
+    if (kind < 0 || kind == 3 || kind > 6) return fail_arg("gpmi_cov: kind must be 0, 1, 2, 4, 5 or 6");
     return cov_impl(c, kind, a, N, b, M, d, p0, p1, nullptr, out);
 }
 
@@ -248,7 +249,7 @@ int gpmi_cov_params(gpmi_ctx* c, int kind, const double* a, int64_t N, const dou
                     const double* params, int nparams, double* out) {
     if (!params) return fail_arg("gpmi_cov_params: null parameters");
     if (kind != 3) {
-        if (kind < 0 || kind > 2 || nparams != 2) return fail_arg("gpmi_cov_params: kinds 0-2 take 2 parameters");
+        if (kind < 0 || kind > 6 || nparams != 2) return fail_arg("gpmi_cov_params: kinds 0-2 and 4-6 take 2 parameters");
         return cov_impl(c, kind, a, N, b, M, d, params[0], params[1], nullptr, out);
     }
     if (nparams != 11) return fail_arg("gpmi_cov_params: the CO2 composite kernel takes 11 hyper-parameters");
@@ -268,7 +269,7 @@ static int cov_impl(gpmi_ctx* c, int kind, const double* a, int64_t N, const dou
     const double sigma = p0, ell = p1;
     if (!c || !a || !b || !out) return fail_arg("gpmi_rbf: null argument");
     if (N < 0 || M < 0 || d <= 0) return fail_arg("gpmi_rbf: bad dimensions");
-    if (kind == 0 && !(ell != 0.0)) return fail_arg("gpmi_rbf: ell must be non-zero");
+    if (cov_stationary(kind) && !(ell != 0.0)) return fail_arg("gpmi_rbf: ell must be non-zero");
     if (kind == 2 && (d != 1 || !(p0 != 0.0) || !(p1 != 0.0)))
         return fail_arg("gpmi_cov: the periodic kernel is 1-D with non-zero period and lengthscale");
     if (N == 0 || M == 0) return GPMI_OK;
@@ -282,7 +283,7 @@ static int cov_impl(gpmi_ctx* c, int kind, const double* a, int64_t N, const dou
     int rc = GPMI_OK;
     hipError_t e;
     double max_sq = -1.0;
-    if (kind == 0) {
+    if (cov_stationary(kind)) {
         Box ba, bb;
         ba.assign(a, N, d);
         bb.assign(b, M, d);
@@ -301,7 +302,7 @@ static int cov_impl(gpmi_ctx* c, int kind, const double* a, int64_t N, const dou
             RbfArgs r;
             r.A = da.as<double>(); r.B = db.as<double>();
             r.nA = N; r.nB = M; r.d = d; r.row0 = r0; r.nrows = round_up(rows, TILE); r.ncols = Mp;
-            r.coef = (kind == 0) ? -.5 * (1 / (ell * ell)) : 0.; r.sig2 = sigma * sigma; r.diag_add = 0.; r.symmetric = 0;
+            r.coef = cov_stationary(kind) ? cov_coef(kind, ell) : 0.; r.sig2 = sigma * sigma; r.diag_add = 0.; r.symmetric = 0;
             r.kind = kind; r.kp0 = p0; r.kp1 = p1;
             if (kpv) for (int i = 0; i < 11; ++i) r.kpv[i] = kpv[i];
             r.delta_square = (N == M) ? 1 : 0;

@@ -128,7 +128,7 @@ struct gpmi_ctx {
     int64_t N = 0, d = 0, Np = 0, ldA = 0, Mp = 0;
     gpmi::Resident res;      // what is resident and what was derived from it: gpmi_state.h, the only place that changes it
     double sig2 = 1.0, coef = -0.5;
-    int kind = 0;            // covariance function: 0 rbf, 1 linear, 2 periodic, 3 CO2 composite (gpmi_set_kernel*)
+    int kind = 0;            // covariance function: 0 rbf, 1 linear, 2 periodic, 3 CO2 composite, 4 / 5 / 6 Matern nu = 1/2, 3/2, 5/2 (gpmi_set_kernel*)
     double kp0 = 0., kp1 = 0.;
     double kpv[11] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
     DevBuf X, y, A, info, red;

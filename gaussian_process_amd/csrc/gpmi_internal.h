@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <mutex>
 
 #include "gpmi_route.h"
@@ -139,7 +140,7 @@ struct RbfArgs {
     int64_t row0;      // first output row (index into A)
     int64_t nrows;     // rows to produce (multiple of 128 incl. padding)
     int64_t ncols;     // cols to produce (multiple of 128 incl. padding)
-    double coef;       // -.5 * (1 / l^2)
+    double coef;       // -.5 * (1 / l^2); the Matern kinds: -a = -sqrt(2 nu) / |l| (cov_coef below)
     double sig2;       // sigma^2
     double diag_add;   // + s on global row == col (symmetric build only)
     int symmetric;     // 1: A==B, lower tiles only, identity padding
@@ -149,16 +150,29 @@ struct RbfArgs {
     // 1 linear  sum_k (a_k - c)(b_k - c), c = kp0            (GP_regression.py:22-33)
     // 2 periodic exp(-2 sin^2(pi |a-b| / p) / l^2), p = kp0, l = kp1, d == 1 (GP_regression.py:36-50)
     // 3 CO2 composite: kernel_1 + kernel_2 + kernel_3 + kernel_4 with theta_1..11 = kpv (CO2_example.py:9-94)
+    // 4 / 5 / 6 Matern nu = 1/2, 3/2, 5/2: sig2 P(t) exp(-t), t = -coef sqrt(sq) (include/gpmi.h: the evaluation order)
     int kind = 0;
     double kp0 = 0., kp1 = 0.;
     double kpv[11] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
     int delta_square = 0;     // kind 3: the reference's output is square -> kernel_4 adds theta_11^2 * eye (:58-59)
     int64_t delta_col0 = 0;   // ... at row == col + delta_col0 (B is a window of the column inputs starting there)
     // upper bound of |a_i - b_j|^2 over the whole launch (from the inputs' bounding boxes), or < 0
-    // when unknown: lets the squared-exponential build skip its per-wave exp domain test
+    // when unknown: lets the squared-exponential and Matern builds skip their per-wave exp domain test
     double max_sq = -1.0;
 };
 hipError_t launch_rbf(hipStream_t s, const RbfArgs& a);
+// The stationary kinds share the register-path K build and the gradient kernels, which take the per-element function
+// as a compile-time family: 0 squared exponential, 1 / 2 / 3 Matern nu = 1/2, 3/2, 5/2 (kinds 4 / 5 / 6).
+inline int cov_family(int kind) { return (kind >= 4 && kind <= 6) ? kind - 3 : 0; }
+inline bool cov_stationary(int kind) { return kind == 0 || cov_family(kind) != 0; }
+// what multiplies sq (family 0: GP_regression.py:19 evaluation order) or sqrt(sq) (Matern: -a) in the exp argument
+inline double cov_coef(int kind, double ell) {
+    static const double two_nu[4] = {0.0, 1.0, 3.0, 5.0};
+    const int f = cov_family(kind);
+    return f ? -(std::sqrt(two_nu[f]) / std::fabs(ell)) : -.5 * (1 / (ell * ell));
+}
+// what the gradients' plain sums are scaled by where the squared exponential has 1 / l^2: a^2 for a Matern kind
+inline double cov_inv_l2(int kind, double ell, double coef) { return cov_family(kind) ? coef * coef : 1.0 / (ell * ell); }
 
 // ---- grad.hip --------------------------------------------------------------
 // sum_ij (alpha_i alpha_j - K_y^-1_ij) dK_ij/dtheta over a block of rows (tune_hyperparms_regression.py:54-57)
@@ -172,7 +186,8 @@ struct GradArgs {
     const double* Kinv;       // (row0 + r, c) at Kinv[r*ld + c]; holds kinv_sign * K_y^-1
     int64_t ld;
     double kinv_sign;
-    double coef, sig2, two_sigma, inv_l3;
+    double coef, sig2, two_sigma, inv_l3;   // family > 0: inv_l3 holds a^2 / l
+    int family = 0;           // cov_family of the kernel
     int tri;                  // 1: symmetric case, lower tiles only (needs row0 == 0, nrows == nB)
     double* partial;          // 2 doubles per block (grad_trace_blocks of them)
 };
@@ -188,7 +203,8 @@ struct GradArdArgs {
     const double* alpha;      // length n
     const double* Kn;         // -K_y^-1, lower tiles valid, leading dimension ld
     int64_t ld;
-    double coef;              // -1 / (2 l^2)
+    double coef;              // -1 / (2 l^2); family > 0: -a
+    int family = 0;           // cov_family of the kernel: the "x" of the sums is then H(t) and sums[width + 1] takes K / sigma^2
     double* partial;          // (width + 3) * grad_ard_blocks doubles, component-major
     double* sums;             // (width + 3) * grad_ard_launches doubles
 };
@@ -210,9 +226,10 @@ hipError_t launch_loo_points(hipStream_t s, const double* y, const double* alpha
                              double* mu, double* var, double* logp, double* sum);
 // upper(i < j) <- lower(j, i) over the np x np matrix (np a multiple of 64)
 hipError_t launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np);
-// D[a][b] = sig2 exp(coef sq_ab) sq_ab for a, b < n and 0 on the padding, np x np in full (np a multiple of 128)
-hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, double* D,
-                           int64_t ld, int64_t np);
+// D[a][b] = sig2 exp(coef sq_ab) sq_ab (family > 0: sig2 H(t_ab) sq_ab, t = -coef sqrt(sq)) for a, b < n and 0 on the
+// padding, np x np in full (np a multiple of 128)
+hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, int family,
+                           double* D, int64_t ld, int64_t np);
 // per row i < n of M: sq[i] = sum_j M_ij^2 (sq may be null), d0[i] = sum_j M_ij x0[j], d1[i] = sum_j M_ij x1[j] (x1, d1
 // may be null); x0, x1 hold at least n + 1 doubles
 hipError_t launch_row_pass(hipStream_t s, const double* M, int64_t ld, int64_t n, const double* x0, const double* x1,

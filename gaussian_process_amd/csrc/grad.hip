@@ -1,5 +1,5 @@
-// grad.hip -- gradient of the log marginal likelihood w.r.t. the squared-exponential
-// hyper-parameters.
+// grad.hip -- gradient of the log marginal likelihood w.r.t. the hyper-parameters of the squared-exponential
+// and Matern kernels.
 //
 // Reference: tune_hyperparms_regression.py:31-64 (gradient_ascent):
 //     l_grad   = sigma**2 * exp(-.5*sqdist/l**2) * (sqdist/l**3)            (:54)
@@ -13,6 +13,15 @@
 // One 128 x 128 tile per block, a column pair x 32 rows per thread, X tiles in LDS
 // (d <= 32) or straight from global memory; per-block partial sums, reduced in a
 // fixed order (bitwise reproducible); the host adds the per-tile partials in order.
+//
+// The three "recompute the kernel element from X, multiply by a weight" kernels (grad_trace_kernel, grad_ard_kernel,
+// loo_dmat_kernel) take the per-element function as a compile-time family F (cov_family: 0 squared exponential,
+// 1 / 2 / 3 Matern nu = 1/2, 3/2, 5/2).  For a Matern, with t = a sqrt(sq), a = -coef:
+//     K / sigma^2 = P(t) e^-t,   dK/dl = sigma^2 a^2 H(t) sq / l,   dK/dz-scale_k likewise with (z_ik - z_jk)^2,
+//     H(t) = -(1/t) d(P e^-t)/dt = e^-t / t,  e^-t,  (1 + t) e^-t / 3
+// H_1/2 is singular at t = 0 but always multiplied by a squared difference <= sq: it is SELECTED to 0 there (duplicate
+// training points), never divided.  Tile enumeration, staging, accumulators and reduction orders are the same for
+// every family, and the family-0 instantiations are the code they were before the families existed.
 #include <algorithm>
 
 #include "exp_dev.h"
@@ -43,7 +52,24 @@ struct GradDev {
     double* partial;        // 2 doubles per block
 };
 
-template <bool LDS>
+// K / sigma^2 = P(t) e^-t and H(t) of Matern family F (1, 2, 3) from the squared distance; coef = -a
+template <int F>
+__device__ __forceinline__ void matern_kh(double coef, double sq, double& k, double& h) {
+    const double t = -coef * sqrt(sq);
+    const double e = exp(-t);
+    if constexpr (F == 1) {
+        k = e;
+        h = (t > 0.0) ? e / t : 0.0;           // a select: sq == 0 (or t underflowed) contributes nothing
+    } else if constexpr (F == 2) {
+        k = (1.0 + t) * e;
+        h = e;
+    } else {
+        k = ((1.0 + t) + (t * t) * (1.0 / 3.0)) * e;
+        h = ((1.0 + t) * e) * (1.0 / 3.0);
+    }
+}
+
+template <bool LDS, int F>
 __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[2][256];
@@ -107,7 +133,13 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
         const double* kp = p.Kinv + ((int64_t)ti * RT + lr) * p.ld + gc;
         const double k0 = (gc < p.nB) ? kp[0] : 0.0;
         const double k1 = (gc + 1 < p.nB) ? kp[1] : 0.0;
-        const double x0 = exp(p.coef * s0), x1 = exp(p.coef * s1);
+        double x0, x1, h0, h1;                                   // K / sigma^2 and what multiplies sq in dK/dl
+        if constexpr (F == 0) {
+            x0 = exp(p.coef * s0); x1 = exp(p.coef * s1);
+        } else {
+            matern_kh<F>(p.coef, s0, x0, h0);
+            matern_kh<F>(p.coef, s1, x1, h1);
+        }
         double w0 = (gc < p.nB) ? fma(ar_, ac0, -p.kinv_sign * k0) : 0.0;
         double w1 = (gc + 1 < p.nB) ? fma(ar_, ac1, -p.kinv_sign * k1) : 0.0;
         if (p.tri) {
@@ -116,8 +148,9 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
             w0 *= (gc < gr) ? 2.0 : (gc == gr) ? 1.0 : 0.0;
             w1 *= (gc + 1 < gr) ? 2.0 : (gc + 1 == gr) ? 1.0 : 0.0;
         }
-        // dK/dl = sigma^2 exp(.) sq / l^3 ; dK/dsigma = 2 sigma exp(.)
-        acc_l += w0 * (p.sig2 * x0 * (s0 * p.inv_l3)) + w1 * (p.sig2 * x1 * (s1 * p.inv_l3));
+        // dK/dl = sigma^2 exp(.) sq / l^3 ; dK/dsigma = 2 sigma exp(.)     (Matern: sigma^2 H sq a^2 / l ; 2 sigma P e^-t)
+        if constexpr (F == 0) acc_l += w0 * (p.sig2 * x0 * (s0 * p.inv_l3)) + w1 * (p.sig2 * x1 * (s1 * p.inv_l3));
+        else acc_l += w0 * (p.sig2 * h0 * (s0 * p.inv_l3)) + w1 * (p.sig2 * h1 * (s1 * p.inv_l3));
         acc_s += w0 * (p.two_sigma * x0) + w1 * (p.two_sigma * x1);
     }
     red[0][tid] = acc_l;
@@ -141,7 +174,8 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
 // and rows per thread; the thread's two columns lie 64 apart so that a wave reads both edges densely), so that gpmi_lml_grad keeps its bits.  Per element: e_k^2 = (z_ik - z_jk)^2 for the DC dimensions of this
 // launch (zero beyond d), x = exp(coef * sum over ALL d of e_k^2), then
 //     acc_k += w x e_k^2,   acc_l += w x sq,   acc_s += w x,   acc_n += w on the diagonal
-// with w = alpha_i alpha_j - K_y^-1_ij, strictly-lower elements counted twice.  The accumulators are indexed by
+// with w = alpha_i alpha_j - K_y^-1_ij, strictly-lower elements counted twice (a Matern family: x = H(t) in acc_k and
+// acc_l, x = P(t) e^-t in acc_s).  The accumulators are indexed by
 // compile-time constants only (every loop over them is unrolled), so they live in registers.  Block partials go out
 // component-major (partial[j * nblk + block]) and are summed by ard_reduce_kernel in a fixed order.
 struct ArdDev {
@@ -156,7 +190,7 @@ struct ArdDev {
     int64_t nblk;
 };
 
-template <int DC, bool LDS>
+template <int DC, bool LDS, int F>
 __global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[4][DC + 3];
@@ -229,11 +263,19 @@ __global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
             double w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
             if (g == gr) acc_n += w;
             else w += w;
-            const double wx = w * exp(p.coef * sq);
+            double wx, ws;                                       // the weight of the lengthscale sums and of sigma's
+            if constexpr (F == 0) {
+                wx = ws = w * exp(p.coef * sq);
+            } else {
+                double kk, hh;
+                matern_kh<F>(p.coef, sq, kk, hh);
+                wx = w * hh;
+                ws = w * kk;
+            }
 #pragma unroll
             for (int k = 0; k < DC; ++k) acc[k] = fma(wx, e2[k], acc[k]);
             acc_l = fma(wx, sq, acc_l);
-            acc_s += wx;
+            acc_s += ws;
         }
     }
     // 64 lanes by a butterfly, then the four waves in order: the same order every run
@@ -341,7 +383,8 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(double* A, int64_t ld
         if (ti != tj || c > r) dst[(int64_t)r * ld + c] = tile[c][r];
 }
 
-// D_ab = K_ab sq_ab = sig2 exp(coef sq_ab) sq_ab in full (dK/dl = D / l^3), zero on padded rows and columns.  The tile
+// D_ab = K_ab sq_ab = sig2 exp(coef sq_ab) sq_ab in full (dK/dl = D / l^3; a Matern family: D_ab = sig2 H(t_ab) sq_ab,
+// dK/dl = a^2 D / l, with the library exp), zero on padded rows and columns.  The tile
 // loop, the staging and the squared distance of grad_trace_kernel; exp by the K build's polynomial while every lane of
 // the wave is inside its domain.  D_ab and D_ba are the same bits ((a - b)^2 == (b - a)^2, the same order over k).
 struct DmatDev {
@@ -353,7 +396,7 @@ struct DmatDev {
     int64_t ld;
 };
 
-template <bool LDS>
+template <bool LDS, int F>
 __global__ __launch_bounds__(256) void loo_dmat_kernel(const DmatDev p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int ti = blockIdx.y, tj = blockIdx.x;
@@ -399,15 +442,21 @@ __global__ __launch_bounds__(256) void loo_dmat_kernel(const DmatDev p) {
                 s1 = fma(e1, e1, s1);
             }
         }
-        const double x0 = p.coef * s0, x1 = p.coef * s1;
         double e0, e1;
-        const bool ok = (x0 >= -700.0) & (x0 <= 0.0) & (x1 >= -700.0) & (x1 <= 0.0);
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
-            e0 = exp_neg_fast(x0);
-            e1 = exp_neg_fast(x1);
+        if constexpr (F == 0) {
+            const double x0 = p.coef * s0, x1 = p.coef * s1;
+            const bool ok = (x0 >= -700.0) & (x0 <= 0.0) & (x1 >= -700.0) & (x1 <= 0.0);
+            if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
+                e0 = exp_neg_fast(x0);
+                e1 = exp_neg_fast(x1);
+            } else {
+                e0 = exp(x0);
+                e1 = exp(x1);
+            }
         } else {
-            e0 = exp(x0);
-            e1 = exp(x1);
+            double k0, k1;
+            matern_kh<F>(p.coef, s0, k0, e0);                    // e = H(t): D = sig2 H sq
+            matern_kh<F>(p.coef, s1, k1, e1);
         }
         dbl2 v;
         v.x = (inr && in0) ? (p.sig2 * e0) * s0 : 0.0;
@@ -516,13 +565,23 @@ int64_t grad_ard_blocks(const GradArdArgs& a) {
 int64_t grad_ard_width(const GradArdArgs& a) { return a.d <= 4 ? 4 : a.d <= 8 ? 8 : a.d <= 16 ? 16 : 32; }
 int64_t grad_ard_launches(const GradArdArgs& a) { return a.d <= GRAD_MAXD ? 1 : (a.d + GRAD_MAXD - 1) / GRAD_MAXD; }
 
-template <int DC>
+template <int DC, int F>
 static void grad_ard_go(hipStream_t s, const ArdDev& p) {
-    hipLaunchKernelGGL((grad_ard_kernel<DC, true>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
+    hipLaunchKernelGGL((grad_ard_kernel<DC, true, F>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
+}
+
+template <int F>
+static void grad_ard_launch(hipStream_t s, const ArdDev& p, int64_t d, int w) {
+    if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, F>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
+    else if (w == 4) grad_ard_go<4, F>(s, p);
+    else if (w == 8) grad_ard_go<8, F>(s, p);
+    else if (w == 16) grad_ard_go<16, F>(s, p);
+    else grad_ard_go<32, F>(s, p);
 }
 
 hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
     if (a.n <= 0 || a.d <= 0) return hipSuccess;
+    if (a.family < 0 || a.family > 3) return hipErrorInvalidValue;
     ArdDev p;
     p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld; p.coef = a.coef;
     p.partial = a.partial; p.nblk = grad_ard_blocks(a);
@@ -530,11 +589,12 @@ hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
     const int64_t nl = grad_ard_launches(a);
     for (int64_t q = 0; q < nl; ++q) {       // d > 32: every launch recomputes the whole squared distance and reads Kn again
         p.k0 = (int)(q * GRAD_MAXD);
-        if (a.d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
-        else if (w == 4) grad_ard_go<4>(s, p);
-        else if (w == 8) grad_ard_go<8>(s, p);
-        else if (w == 16) grad_ard_go<16>(s, p);
-        else grad_ard_go<32>(s, p);
+        switch (a.family) {
+            case 0: grad_ard_launch<0>(s, p, a.d, w); break;
+            case 1: grad_ard_launch<1>(s, p, a.d, w); break;
+            case 2: grad_ard_launch<2>(s, p, a.d, w); break;
+            default: grad_ard_launch<3>(s, p, a.d, w); break;
+        }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(ard_reduce_kernel, dim3((unsigned)(w + 3)), dim3(256), 0, s, a.partial, p.nblk, a.sums + q * (w + 3));
@@ -558,13 +618,19 @@ hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a) {
     p.Kinv = a.Kinv; p.ld = a.ld; p.kinv_sign = a.kinv_sign;
     p.coef = a.coef; p.sig2 = a.sig2; p.two_sigma = a.two_sigma; p.inv_l3 = a.inv_l3;
     p.tri = a.tri; p.partial = a.partial;
+    if (a.family < 0 || a.family > 3) return hipErrorInvalidValue;
     const dim3 grid((unsigned)grad_trace_blocks(a)), block(256);
-    if (a.d <= GRAD_MAXD) {
-        const size_t lds = (size_t)2 * RT * a.d * sizeof(double);
-        hipLaunchKernelGGL(grad_trace_kernel<true>, grid, block, lds, s, p);
-    } else {
-        hipLaunchKernelGGL(grad_trace_kernel<false>, grid, block, 0, s, p);
+    const size_t lds = (size_t)2 * RT * a.d * sizeof(double);
+#define GRAD_TRACE_FAMILY(FF)                                                                                          \
+    if (a.d <= GRAD_MAXD) hipLaunchKernelGGL((grad_trace_kernel<true, FF>), grid, block, lds, s, p);                   \
+    else hipLaunchKernelGGL((grad_trace_kernel<false, FF>), grid, block, 0, s, p)
+    switch (a.family) {
+        case 0: GRAD_TRACE_FAMILY(0); break;
+        case 1: GRAD_TRACE_FAMILY(1); break;
+        case 2: GRAD_TRACE_FAMILY(2); break;
+        default: GRAD_TRACE_FAMILY(3); break;
     }
+#undef GRAD_TRACE_FAMILY
     return hipGetLastError();
 }
 
@@ -591,14 +657,23 @@ hipError_t launch_mirror_lower(hipStream_t s, double* A, int64_t ld, int64_t np)
     return hipGetLastError();
 }
 
-hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, double* D,
-                           int64_t ld, int64_t np) {
+hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d, double coef, double sig2, int family,
+                           double* D, int64_t ld, int64_t np) {
     if (np <= 0 || d <= 0) return hipSuccess;
+    if (family < 0 || family > 3) return hipErrorInvalidValue;
     DmatDev p;
     p.Z = Z; p.n = n; p.d = (int)d; p.coef = coef; p.sig2 = sig2; p.D = D; p.ld = ld;
     const unsigned T = (unsigned)(np / RT);
-    if (d <= GRAD_MAXD) hipLaunchKernelGGL(loo_dmat_kernel<true>, dim3(T, T), dim3(256), (size_t)2 * RT * d * sizeof(double), s, p);
-    else hipLaunchKernelGGL(loo_dmat_kernel<false>, dim3(T, T), dim3(256), 0, s, p);
+#define LOO_DMAT_FAMILY(FF)                                                                                            \
+    if (d <= GRAD_MAXD) hipLaunchKernelGGL((loo_dmat_kernel<true, FF>), dim3(T, T), dim3(256), (size_t)2 * RT * d * sizeof(double), s, p); \
+    else hipLaunchKernelGGL((loo_dmat_kernel<false, FF>), dim3(T, T), dim3(256), 0, s, p)
+    switch (family) {
+        case 0: LOO_DMAT_FAMILY(0); break;
+        case 1: LOO_DMAT_FAMILY(1); break;
+        case 2: LOO_DMAT_FAMILY(2); break;
+        default: LOO_DMAT_FAMILY(3); break;
+    }
+#undef LOO_DMAT_FAMILY
     return hipGetLastError();
 }
 

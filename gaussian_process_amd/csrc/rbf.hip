@@ -14,6 +14,14 @@
 // exp, one multiplication by sigma^2.  Only exp() itself may differ from
 // NumPy's (both are < 1 ulp).
 //
+// The Matern kinds 4 / 5 / 6 (nu = 1/2, 3/2, 5/2; include/gpmi.h) share everything but the per-element finish, which
+// is a compile-time family F (0 squared exponential, 1 / 2 / 3 the Materns; cov_family):
+//   out[i][j] = sig2 * (P(t) * exp(-t)),  t = a * sqrt(sq),  a = -coef = sqrt(2 nu) / |l|
+//   P = 1,  1 + t,  (1 + t) + (t * t) * c3  (c3 the double nearest 1/3)
+// sqrt is the correctly rounded one, every operation rounds once (no contraction), and the exp argument -t goes
+// through the same table exp, wave-wide domain test and library fallback as coef * sq.  At sq == 0 every factor is
+// exactly 1.  The family-0 instantiations are the code they were before the families existed.
+//
 // HBM-write bound: a block produces a 128 x 128 tile; a wavefront writes whole
 // 1-KiB row segments (64 lanes x 16 B).  The x rows of both tile edges are
 // staged once in LDS; for the common d (1..8, 16) the b values of a thread's two
@@ -132,6 +140,26 @@ __device__ __forceinline__ void exp_pair_tab(double x0, double x1, double& e0, d
     }
 }
 
+// the exp argument of family F from the squared distance: coef * sq, or -t = (-a) * sqrt(sq)
+template <int F>
+__device__ __forceinline__ double cov_arg(double coef, double s) {
+    if constexpr (F == 0) return coef * s;
+    else return coef * sqrt(s);
+}
+
+// P(t) * e for x = -t (e = exp(x)); families 0 and 1 have P = 1
+template <int F>
+__device__ __forceinline__ double cov_poly(double x, double e) {
+    if constexpr (F <= 1) {
+        return e;
+    } else {
+        const double t = -x;
+        double P = 1.0 + t;
+        if constexpr (F == 3) P = P + (t * t) * 0.33333333333333331;
+        return P * e;
+    }
+}
+
 template <int D, class FA, class FB>
 __device__ __forceinline__ double sq_pw_static(FA a, FB b) {
     if constexpr (D < 8) {
@@ -181,11 +209,13 @@ __device__ __forceinline__ bool rbf_map_tile(const RbfDev& p, int& ti, int& tj) 
 __device__ __forceinline__ void cov_store(const RbfDev& p, int64_t gr, int64_t gc, double v0, double v1,
                                           double* dst);
 
+template <int F>
 __device__ __forceinline__ void rbf_finish(const RbfDev& p, int64_t gr, int64_t gc, double s0, double s1,
                                            double* dst) {
+    const double x0 = cov_arg<F>(p.coef, s0), x1 = cov_arg<F>(p.coef, s1);
     double e0, e1;
-    exp_pair(p.coef * s0, p.coef * s1, e0, e1);
-    cov_store(p, gr, gc, p.sig2 * e0, p.sig2 * e1, dst);
+    exp_pair(x0, x1, e0, e1);
+    cov_store(p, gr, gc, p.sig2 * cov_poly<F>(x0, e0), p.sig2 * cov_poly<F>(x1, e1), dst);
 }
 
 // diagonal term, identity / zero padding, 16-byte store of a column pair
@@ -251,8 +281,8 @@ __device__ __forceinline__ double cov_other(const RbfDev& p, const double* a, co
     return cov_other_acc(p, [&](int k) { return a[k]; }, [&](int k) { return b[k]; }, diag);
 }
 
-// D > 0: d == D at compile time (b columns in registers); D == 0: runtime d <= LDS_MAXD
-template <int D>
+// D > 0: d == D at compile time (b columns in registers); D == 0: runtime d <= LDS_MAXD.  F: the family
+template <int D, int F = 0>
 __global__ __launch_bounds__(256) void rbf_kernel(const RbfDev p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int d = D ? D : p.d;
@@ -290,10 +320,10 @@ __global__ __launch_bounds__(256) void rbf_kernel(const RbfDev p) {
             for (int k = 0; k < D; ++k) av[k] = ar[k];
             const double s0 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b0[k]; });
             const double s1 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b1[k]; });
-            rbf_finish(p, grow0 + 32 * rg + r, gc, s0, s1, out0 + (int64_t)r * p.ld);
+            rbf_finish<F>(p, grow0 + 32 * rg + r, gc, s0, s1, out0 + (int64_t)r * p.ld);
         }
     } else {
-        if (p.kind != 0) {
+        if (F == 0 && p.kind != 0) {
             // the reference's other covariance functions through the same tile: X rows of both tile edges in LDS
             // (a: broadcast reads, b: conflict-free column reads), one column pair x 32 rows per thread
             for (int r = 0; r < 32; ++r) {
@@ -314,7 +344,7 @@ __global__ __launch_bounds__(256) void rbf_kernel(const RbfDev p) {
             const double* bc = &Bs[2 * cp];
             const double s0 = sq_pw_small([&](int k) { return ar[k]; }, [&](int k) { return bc[k * RT]; }, d);
             const double s1 = sq_pw_small([&](int k) { return ar[k]; }, [&](int k) { return bc[k * RT + 1]; }, d);
-            rbf_finish(p, grow0 + 32 * rg + r, gc, s0, s1, out0 + (int64_t)r * p.ld);
+            rbf_finish<F>(p, grow0 + 32 * rg + r, gc, s0, s1, out0 + (int64_t)r * p.ld);
         }
     }
 }
@@ -355,7 +385,7 @@ __device__ __forceinline__ void rbf_load_cols(const RbfDev& p, const double* __r
     }
 }
 
-template <int D, bool EDGE, bool CHECK = true, bool UNIT = false>
+template <int D, int F, bool EDGE, bool CHECK = true, bool UNIT = false>
 __device__ __forceinline__ void rbf_tile_rows(const RbfDev& p, const double* __restrict__ Ap,
                                               double* __restrict__ outp, int64_t grow0, int64_t gcol0, int ti,
                                               const double (&b0)[D], const double (&b1)[D], const double* tab) {
@@ -373,9 +403,10 @@ __device__ __forceinline__ void rbf_tile_rows(const RbfDev& p, const double* __r
             for (int k = 0; k < D; ++k) av[k] = ar[k];               // scalar loads (uniform address)
             const double s0 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b0[k]; });
             const double s1 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b1[k]; });
+            const double x0 = cov_arg<F>(p.coef, s0), x1 = cov_arg<F>(p.coef, s1);
             double e0, e1;
-            exp_pair_tab(p.coef * s0, p.coef * s1, e0, e1, tab);
-            cov_store(p, gr, gc, p.sig2 * e0, p.sig2 * e1, out0 + (int64_t)r * p.ld);
+            exp_pair_tab(x0, x1, e0, e1, tab);
+            cov_store(p, gr, gc, p.sig2 * cov_poly<F>(x0, e0), p.sig2 * cov_poly<F>(x1, e1), out0 + (int64_t)r * p.ld);
         }
     } else {
         // wave-uniform row base + constant 32-bit lane offset: the store takes the scalar-base form
@@ -390,13 +421,16 @@ __device__ __forceinline__ void rbf_tile_rows(const RbfDev& p, const double* __r
             for (int k = 0; k < D; ++k) av[k] = ar[k];               // scalar loads (uniform address)
             const double s0 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b0[k]; });
             const double s1 = sq_pw_static<D>([&](int k) { return av[k]; }, [&](int k) { return b1[k]; });
+            const double x0 = cov_arg<F>(p.coef, s0), x1 = cov_arg<F>(p.coef, s1);
             double e0, e1;
             if constexpr (CHECK) {
-                exp_pair_tab(p.coef * s0, p.coef * s1, e0, e1, tab);
+                exp_pair_tab(x0, x1, e0, e1, tab);
             } else {
-                e0 = exp_neg_tab(p.coef * s0, tab);
-                e1 = exp_neg_tab(p.coef * s1, tab);
+                e0 = exp_neg_tab(x0, tab);
+                e1 = exp_neg_tab(x1, tab);
             }
+            e0 = cov_poly<F>(x0, e0);
+            e1 = cov_poly<F>(x1, e1);
             if constexpr (!UNIT) { e0 = p.sig2 * e0; e1 = p.sig2 * e1; }   // sigma^2 == 1: the product is exact
             // global_store with SGPR base: the per-row address costs no vector instruction
             const d2 ev = d2{e0, e1};
@@ -408,7 +442,7 @@ __device__ __forceinline__ void rbf_tile_rows(const RbfDev& p, const double* __r
 // Work item = (strip of p.strip row tiles, column tile), column tile fastest.  Blocks are
 // persistent: block b takes items b, b + gridDim.x, ... (a bare store stream in this pattern
 // runs 10 % faster from persistent blocks than from one short block per item).
-template <int D>
+template <int D, int F>
 __global__ __launch_bounds__(256) void rbf_regs_kernel(const double* __restrict__ Ap, const double* __restrict__ Bp,
                                                         double* __restrict__ outp, const RbfDev p) {
     __shared__ __attribute__((aligned(16))) double tab[EXP_TAB];
@@ -436,20 +470,21 @@ __global__ __launch_bounds__(256) void rbf_regs_kernel(const double* __restrict_
                 // launch-uniform specialisations of the interior loop: no per-wave domain test when the
                 // host has bounded the arguments, no sigma^2 multiply when it is 1 (the reference's default)
                 if (p.nocheck) {
-                    if (unit) rbf_tile_rows<D, false, false, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
-                    else rbf_tile_rows<D, false, false, false>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
+                    if (unit) rbf_tile_rows<D, F, false, false, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
+                    else rbf_tile_rows<D, F, false, false, false>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
                 } else {
-                    if (unit) rbf_tile_rows<D, false, true, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
-                    else rbf_tile_rows<D, false, true, false>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
+                    if (unit) rbf_tile_rows<D, F, false, true, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
+                    else rbf_tile_rows<D, F, false, true, false>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
                 }
             } else {
-                rbf_tile_rows<D, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
+                rbf_tile_rows<D, F, true>(p, Ap, outp, grow0, gcol0, ti, b0, b1, tab);
             }
         }
     }
 }
 
 // any d: operands straight from global memory (L2-resident), one column pair per thread
+template <int F>
 __global__ __launch_bounds__(256) void rbf_naive_kernel(const RbfDev p) {
     int ti, tj;
     if (!rbf_map_tile(p, ti, tj)) return;
@@ -465,7 +500,7 @@ __global__ __launch_bounds__(256) void rbf_naive_kernel(const RbfDev p) {
             if (gc < p.nB) s0 = sq_pw_global(p.A + gr * d, p.B + gc * d, d);
             if (gc + 1 < p.nB) s1 = sq_pw_global(p.A + gr * d, p.B + (gc + 1) * d, d);
         }
-        rbf_finish(p, gr, gc, s0, s1, p.out + ((int64_t)ti * RT + 32 * rg + r) * p.ld + gc);
+        rbf_finish<F>(p, gr, gc, s0, s1, p.out + ((int64_t)ti * RT + 32 * rg + r) * p.ld + gc);
     }
 }
 
@@ -519,14 +554,17 @@ hipError_t launch_rbf(hipStream_t s, const RbfArgs& a) {
     for (int i = 0; i < 11; ++i) p.kpv[i] = a.kpv[i];
     p.delta_square = a.delta_square;
     p.delta_col0 = a.delta_col0;
-    // coef <= 0 and max_sq bounds every squared distance of this launch (NaN / unknown fail the test)
-    p.nocheck = (a.max_sq >= 0.0 && a.coef <= 0.0 && a.coef * a.max_sq * 1.000001 >= -690.0) ? 1 : 0;
-    if (a.kind < 0 || a.kind > 3 || (a.kind == 2 && a.d != 1)) return hipErrorInvalidValue;
+    if (a.kind < 0 || a.kind > 6 || (a.kind == 2 && a.d != 1)) return hipErrorInvalidValue;
+    const int fam = cov_family(a.kind);
+    // coef <= 0 and max_sq bounds every squared distance of this launch (NaN / unknown fail the test); a Matern's
+    // argument is coef * sqrt(sq)
+    const double max_arg = fam ? a.coef * std::sqrt(a.max_sq) : a.coef * a.max_sq;
+    p.nocheck = (a.max_sq >= 0.0 && a.coef <= 0.0 && max_arg * 1.000001 >= -690.0) ? 1 : 0;
     p.tri = (a.symmetric && a.row0 == 0 && p.Tm == p.Tn) ? 1 : 0;
     const int64_t nblk = p.tri ? (int64_t)p.Tm * (p.Tm + 1) / 2 : (int64_t)p.Tm * p.Tn;
     dim3 grid((unsigned)nblk), block(256);
     const size_t lds = (size_t)2 * RT * a.d * sizeof(double);
-    if (a.kind != 0) {
+    if (!cov_stationary(a.kind)) {
         // lin / per / CO2 composite: the LDS-staged tile kernel (d <= 32), straight from global memory above that
         if (a.d <= LDS_MAXD) hipLaunchKernelGGL(rbf_kernel<0>, grid, block, lds, s, p);
         else hipLaunchKernelGGL(cov_other_kernel, grid, block, 0, s, p);
@@ -540,16 +578,24 @@ hipError_t launch_rbf(hipStream_t s, const RbfArgs& a) {
     p.strip = (nblk >= 4096) ? 4 : 1;
     p.nitems = p.Tn * ((p.Tm + p.strip - 1) / p.strip);
     const dim3 sgrid((unsigned)std::min<int64_t>(p.nitems, tuning().rbf_blocks));
-#define RBF_CASE(DD) case DD: hipLaunchKernelGGL(rbf_regs_kernel<DD>, sgrid, block, 0, s, p.A, p.B, p.out, p); break
-    if (a.d > LDS_MAXD) {
-        hipLaunchKernelGGL(rbf_naive_kernel, grid, block, 0, s, p);
-    } else {
-        switch (a.d) {
-            RBF_CASE(1); RBF_CASE(2); RBF_CASE(3); RBF_CASE(4); RBF_CASE(5); RBF_CASE(6); RBF_CASE(7);
-            RBF_CASE(8); RBF_CASE(16);
-            default: hipLaunchKernelGGL(rbf_kernel<0>, grid, block, lds, s, p); break;
-        }
+#define RBF_CASE(DD, FF) case DD: hipLaunchKernelGGL((rbf_regs_kernel<DD, FF>), sgrid, block, 0, s, p.A, p.B, p.out, p); break
+#define RBF_FAMILY(FF)                                                                                                 \
+    if (a.d > LDS_MAXD) {                                                                                              \
+        hipLaunchKernelGGL(rbf_naive_kernel<FF>, grid, block, 0, s, p);                                                \
+    } else {                                                                                                           \
+        switch (a.d) {                                                                                                 \
+            RBF_CASE(1, FF); RBF_CASE(2, FF); RBF_CASE(3, FF); RBF_CASE(4, FF); RBF_CASE(5, FF); RBF_CASE(6, FF);      \
+            RBF_CASE(7, FF); RBF_CASE(8, FF); RBF_CASE(16, FF);                                                        \
+            default: hipLaunchKernelGGL((rbf_kernel<0, FF>), grid, block, lds, s, p); break;                           \
+        }                                                                                                              \
     }
+    switch (fam) {
+        case 0: RBF_FAMILY(0) break;
+        case 1: RBF_FAMILY(1) break;
+        case 2: RBF_FAMILY(2) break;
+        default: RBF_FAMILY(3) break;
+    }
+#undef RBF_FAMILY
 #undef RBF_CASE
     return hipGetLastError();
 }

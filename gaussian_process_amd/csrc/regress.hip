@@ -101,13 +101,13 @@ int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
 }
 
 // The front of both LML gradients and of the leave-one-out calls: the resident factorisation and -- rbf_only not null --
-// its kernel checked with the caller's own texts, the slot's timer reset, and inside a span of that slot, which it opens:
+// its kernel (kinds 0, 4, 5, 6: the stationary ones the gradient kernels have a family for) checked with the caller's own texts, the slot's timer reset, and inside a span of that slot, which it opens:
 // alpha = L^-T m (a5; solve_epilogue reads the backward solve's give-up word), U = L^-T by the TRSM sweep on the identity
 // and -- want_kn -- Kn = -U U^T on the lower tiles.
 static int grad_front(gpmi_ctx* c, const char* not_resident, const char* rbf_only, int slot, bool want_kn, double** alpha_out,
                       size_t* span) {
     if (!c->res.regression()) return fail_arg(not_resident);
-    if (rbf_only && c->kind != 0) return fail_arg(rbf_only);
+    if (rbf_only && !cov_stationary(c->kind)) return fail_arg(rbf_only);
     c->timers_reset({slot});
     const int64_t Np = c->Np, ld = c->ldA;
     HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
@@ -129,7 +129,7 @@ int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     double* alpha = nullptr;
     size_t sp = 0;
     int rc = grad_front(c, "gpmi_lml_grad: no factorisation resident (call gpmi_factorize)",
-                        "gpmi_lml_grad: squared-exponential kernel only (tune_hyperparms_regression.py:54)", GPMI_T_GRAD, true,
+                        "gpmi_lml_grad: squared-exponential or Matern kernel only (kinds 0, 4, 5, 6)", GPMI_T_GRAD, true,
                         &alpha, &sp);
     if (rc) return rc;
     hipStream_t s = c->stream;
@@ -139,7 +139,9 @@ int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma) {
     a.alpha_r = a.alpha_c = alpha;
     a.Kinv = c->Kn.as<double>(); a.ld = c->ldA; a.kinv_sign = -1.0;
     a.coef = c->coef; a.sig2 = c->sig2; a.two_sigma = 2 * c->sigma;
-    a.inv_l3 = 1.0 / (c->ell * c->ell * c->ell);
+    a.family = cov_family(c->kind);
+    // dK/dl = K sq / l^3; a Matern: sigma^2 H sq a^2 / l
+    a.inv_l3 = a.family ? cov_inv_l2(c->kind, c->ell, c->coef) / c->ell : 1.0 / (c->ell * c->ell * c->ell);
     a.tri = 1;
     const int64_t nblk = grad_trace_blocks(a);
     HIP_TRY(c->gpart.ensure((size_t)nblk * 16));
@@ -163,12 +165,13 @@ int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     double* alpha = nullptr;
     size_t sp = 0;
     int rc = grad_front(c, "gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)",
-                        "gpmi_lml_grad_ard: squared-exponential kernel only", GPMI_T_GRAD, true, &alpha, &sp);
+                        "gpmi_lml_grad_ard: squared-exponential or Matern kernel only (kinds 0, 4, 5, 6)", GPMI_T_GRAD, true, &alpha, &sp);
     if (rc) return rc;
     hipStream_t s = c->stream;
     GradArdArgs a;
     a.Z = c->x_train(); a.n = c->N; a.d = c->d;
     a.alpha = alpha; a.Kn = c->Kn.as<double>(); a.ld = c->ldA; a.coef = c->coef;
+    a.family = cov_family(c->kind);
     const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
     HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
     HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
@@ -179,8 +182,9 @@ int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     std::vector<double> sums((size_t)nl * (size_t)(w + 3));
     HIP_TRY(hipMemcpyAsync(sums.data(), a.sums, sums.size() * 8, hipMemcpyDeviceToHost, s));
     if ((rc = solve_epilogue(c, "gpmi_lml_grad_ard"))) return rc;
-    // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums
-    const double l2 = c->ell * c->ell;
+    // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums; a Matern
+    // kind has H(t) for K/sigma^2 in the lengthscale sums and a^2 for 1 / l^2
+    const double l2 = a.family ? 1.0 / cov_inv_l2(c->kind, c->ell, c->coef) : c->ell * c->ell;
     if (d_r)
         for (int64_t k = 0; k < c->d; ++k) {
             const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
@@ -231,7 +235,7 @@ int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) 
     double* alpha = nullptr;
     size_t sp = 0;
     int rc = grad_front(c, "gpmi_loo_grad: no regression factorisation resident (call gpmi_factorize)",
-                        "gpmi_loo_grad: squared-exponential kernel only", GPMI_T_LOO, true, &alpha, &sp);
+                        "gpmi_loo_grad: squared-exponential or Matern kernel only (kinds 0, 4, 5, 6)", GPMI_T_LOO, true, &alpha, &sp);
     if (rc) return rc;
     hipStream_t s = c->stream;
     const int64_t N = c->N, Np = c->Np, ld = c->ldA;
@@ -243,7 +247,7 @@ int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) 
     double *D = c->U.as<double>(), *Kn = c->Kn.as<double>(), *W = c->loow.as<double>();
     HIP_TRY(launch_loo_kappa(s, D, ld, N, kappa));               // U is still L^-T here
     HIP_TRY(launch_mirror_lower(s, Kn, ld, Np));
-    HIP_TRY(launch_loo_dmat(s, c->x_train(), N, c->d, c->coef, c->sig2, D, ld, Np));
+    HIP_TRY(launch_loo_dmat(s, c->x_train(), N, c->d, c->coef, c->sig2, cov_family(c->kind), D, ld, Np));
     HIP_TRY(launch_row_pass(s, D, ld, N, alpha, nullptr, nullptr, t, nullptr));
     HIP_TRY(launch_row_pass(s, Kn, ld, N, alpha, t, cn, qn, un));
     for (int64_t r0 = 0; r0 < N; r0 += NB) {                     // a row block of padding only has nothing to give
@@ -261,7 +265,8 @@ int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) 
     double h[3] = {0.0, 0.0, 0.0};
     HIP_TRY(hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, s));
     if ((rc = solve_epilogue(c, "gpmi_loo_grad"))) return rc;
-    if (d_ell) *d_ell = h[0] / (c->ell * c->ell * c->ell);
+    if (d_ell) *d_ell = cov_family(c->kind) ? h[0] * (cov_inv_l2(c->kind, c->ell, c->coef) / c->ell)      // dK/dl = a^2 D / l
+                                            : h[0] / (c->ell * c->ell * c->ell);
     if (d_sigma) *d_sigma = 2.0 / c->sigma * h[1];
     if (d_noise) *d_noise = h[2];
     return GPMI_OK;
@@ -272,6 +277,7 @@ int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise) 
 int grad_trace_impl(gpmi_ctx* c, const double* a_in, const double* b_in, int64_t N, int64_t d, double sigma, double ell,
                     const double* alpha_in, const double* Kinv_in, double* d_ell, double* d_sigma) {
     if (N <= 0 || d <= 0) return fail_arg("gpmi_grad_trace: N and d must be positive");
+    if (cov_family(c->kind)) return fail_arg("gpmi_grad_trace: squared-exponential kernel only (the context is set to a Matern kind)");
     if (!(ell != 0.0)) return fail_arg("gpmi_grad_trace: ell must be non-zero");
     hipStream_t s = c->stream;
     DevBuf da, db, dal, dk, dp;

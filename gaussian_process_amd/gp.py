@@ -168,11 +168,15 @@ class GPContext:
                                  scalar(sigma, "sigma"), scalar(l, "l"), ptr(out)))
         return out
 
-    KINDS = {"rbf": 0, "lin": 1, "per": 2, "co2": 3}
+    KINDS = {"rbf": 0, "lin": 1, "per": 2, "co2": 3, "matern12": 4, "matern32": 5, "matern52": 6}
+    MATERN = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}      # nu -> the kind's name
 
     def cov(self, kind, a, b, p0, p1=0.0):
         """kernel matrix of the reference's covariance functions: 'rbf' (p0 = sigma, p1 = l),
-        'lin' (p0 = c), 'per' (p0 = period, p1 = lengthscale; 1-D inputs)"""
+        'lin' (p0 = c), 'per' (p0 = period, p1 = lengthscale; 1-D inputs), and the Matern family 'matern12' /
+        'matern32' / 'matern52' (nu = 1/2, 3/2, 5/2; p0 = sigma, p1 = l)"""
+        if kind not in self.KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (sorted(self.KINDS), kind))
         a = as_f64(a, 2, "a")
         b = as_f64(b, 2, "b")
         if a.shape[1] != b.shape[1]:
@@ -189,7 +193,10 @@ class GPContext:
 
     def set_kernel(self, kind, p0=0.0, p1=0.0):
         """covariance function of the following fit / predict calls (kernel_choice of prediction());
-        'co2': p0 = the 11 hyper-parameters of CO2_example.py's covariance_function"""
+        'co2': p0 = the 11 hyper-parameters of CO2_example.py's covariance_function; 'matern12' / 'matern32' /
+        'matern52' take sigma and l from the fitting call, as 'rbf' does"""
+        if kind not in self.KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (sorted(self.KINDS), kind))
         if kind == "co2":
             th = as_f64(np.asarray(p0, dtype=np.float64).reshape(-1), 1, "hyperparms")
             check(self._lib.gpmi_set_kernel_params(self._h, 3, ptr(th), th.shape[0]))
@@ -216,7 +223,8 @@ class GPContext:
 
     def set_lengthscales(self, r):
         """Relative per-dimension lengthscales r_k > 0 (ARD): from now on this context's squared-exponential covariance
-        is sigma**2 exp(-.5 / l**2 * sum_k ((x_ik - x_jk) / r_k)**2) in every fit, prediction and gradient.  None
+        is sigma**2 exp(-.5 / l**2 * sum_k ((x_ik - x_jk) / r_k)**2) in every fit, prediction and gradient (a Matern
+        covariance takes the same scaled squared distance).  None
         returns it to the isotropic state.  Whatever was fitted is dropped; the inputs stay on the device."""
         if r is None:
             check(self._lib.gpmi_set_lengthscales(self._h, None, 0))
@@ -365,7 +373,7 @@ class GPContext:
 
     def loo_grad(self):
         """(d/dl, d/dsigma, d/dnoise_var) of the leave-one-out log probability at the resident factorisation (GPML
-        eq. 5.13; squared-exponential kernel, gpmi_loo_grad)."""
+        eq. 5.13; squared-exponential or Matern kernel, gpmi_loo_grad)."""
         dl, ds, dn = C.c_double(), C.c_double(), C.c_double()
         check(self._lib.gpmi_loo_grad(self._h, C.byref(dl), C.byref(ds), C.byref(dn)))
         return dl.value, ds.value, dn.value

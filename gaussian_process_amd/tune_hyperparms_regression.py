@@ -11,24 +11,39 @@ import numpy as np
 from .gp import default_context, split_lengthscale
 
 NOISE_VAR = 0.0005      # tune_hyperparms_regression.py:302
+
+
+def _use_kernel(ctx, kernel):
+    """The kernel= keyword of the LML / LOO functions below: 'rbf' (the reference's, the default) or a Matern
+    ('matern12', 'matern32', 'matern52').  Set on the context on every call, the way prediction() selects its kernel --
+    and left there, with the factorisation the call made: a later call without the keyword sets 'rbf' again, a caller who
+    goes on with the context directly finds the kernel of the last call."""
+    from .GP_regression import _check_stationary
+    kernel = _check_stationary(kernel)
+    ctx.set_kernel(kernel)
 BO_NOISE_VAR = 0.0001   # tune_hyperparms_regression.py:75
 
 
 def compute_mar_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None, n_gpus=None,
-                           dist=None):
+                           dist=None, kernel="rbf"):
     """Log marginal likelihood, reference tune_hyperparms_regression.py:292-313.
     X_test is accepted and unused, exactly as in the reference.  l may be a d-vector (one lengthscale per input
     dimension); a scalar or 1-element l is isotropic and clears any the context carried.  n_gpus / dist: factorise with the covariance
-    row-block partitioned over the ranks of the node (every rank makes the same call)."""
-    from .GP_regression import _dist_of
+    row-block partitioned over the ranks of the node (every rank makes the same call).  kernel: 'rbf' or a Matern
+    ('matern12', 'matern32', 'matern52'; not on the partitioned path)."""
+    from .GP_regression import _check_stationary, _dist_of
+    _check_stationary(kernel)
     l, r = split_lengthscale(l)          # a d-vector: one lengthscale per input dimension, common l = 1
     gp = _dist_of(n_gpus, dist)
     if gp is not None:
+        if kernel != "rbf":
+            raise ValueError("the Matern kernels are not available on the partitioned path (n_gpus / dist)")
         if r is not None:
             raise ValueError("per-dimension lengthscales (a vector l) are not available on the partitioned path (n_gpus / dist)")
         from ._lib import scalar
         return np.float64(gp.fit(X_train, y_train, scalar(sigma, "sigma"), scalar(l, "l"), noise_var))
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     try:
         return np.float64(ctx.fit(X_train, y_train, sigma, l, noise_var, lengthscales=r))
     finally:
@@ -36,11 +51,12 @@ def compute_mar_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOIS
             ctx.set_lengthscales(None)   # the lengthscales of this call do not outlive it
 
 
-def compute_mar_likelihood_batch(X_train, y_train, triples, *, ctx=None):
+def compute_mar_likelihood_batch(X_train, y_train, triples, *, ctx=None, kernel="rbf"):
     """The reference's `for i in range(len(l)): compute_mar_likelihood(...)` loops
     (:368-369, :385-386) as one call: triples is (T, 3) rows of
-    (l, sigma_f, noise_var).  Returns lml (T,), NaN where K + sI was not PD."""
+    (l, sigma_f, noise_var).  Returns lml (T,), NaN where K + sI was not PD.  kernel as compute_mar_likelihood."""
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     ctx.set_train(X_train, y_train)
     lml, _ = ctx.lml_batch(triples)
     return lml
@@ -215,10 +231,11 @@ def gradient_ascent(a, b, sigma, l, alpha, K_y, *, ctx=None):
     return sigma, l + GA_STEP_SIZE * l_var                       # :63
 
 
-def lml_and_gradient(X_train, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None):
+def lml_and_gradient(X_train, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None, kernel="rbf"):
     """LML (:141) and (dLML/dl, dLML/dsigma) (:54-57, :46-51) at (sigma, l) with everything
-    resident on the device: the body of the tuner's loop without its predictive part."""
+    resident on the device: the body of the tuner's loop without its predictive part.  kernel: 'rbf' or a Matern."""
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     lml = ctx.fit(X_train, y_train, sigma, l, noise_var)
     dl, ds = ctx.lml_grad()
     return np.float64(lml), dl, ds
@@ -289,11 +306,12 @@ def _ard_lml(ctx, lengthscales, sigma, noise_var):
         return -np.inf
 
 
-def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOISE_VAR, ctx=None):
-    """(lml, d_lengthscales (d,), d_sigma, d_noise): the log marginal likelihood of the squared-exponential kernel with one
+def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOISE_VAR, ctx=None, kernel="rbf"):
+    """(lml, d_lengthscales (d,), d_sigma, d_noise): the log marginal likelihood of the squared-exponential (or, kernel=, a Matern) kernel with one
     absolute lengthscale per input dimension, and its derivatives w.r.t. those lengthscales, sigma and noise_var.  The
     context keeps the lengthscales and the factorisation (alpha, predict and lml_grad_ard work on it afterwards)."""
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     ls = np.asarray(lengthscales, dtype=np.float64).reshape(-1)
     lml = ctx.fit(X_train, y_train, sigma, 1.0, noise_var, lengthscales=ls)
     d_r, _, d_sigma, d_noise = ctx.lml_grad_ard()      # common l = 1: d_r is the derivative w.r.t. the lengthscales
@@ -342,7 +360,7 @@ def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=Fals
 
 
 def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise_var=NOISE_VAR, max_iter=100, tol=1e-6,
-                        ctx=None):
+                        ctx=None, kernel="rbf"):
     """Maximise the log marginal likelihood over (lengthscales, sigma, noise_var) by gradient ascent on their logarithms.
 
     Every iteration takes the gradient at the current point (d LML / d log p = p * d LML / d p) and tries a step along
@@ -352,10 +370,12 @@ def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise
     iterations or when |dLML| <= tol * max(1, |LML|).
 
     :param lengthscales: initial per-dimension lengthscales (default: all 1)
+    :param kernel: 'rbf' or a Matern ('matern12', 'matern32', 'matern52'); the context keeps it
     :return: (lengthscales (d,), sigma, noise_var, lml, trace): the parameters reached, their LML and the LML of every
              accepted point, the initial one first.  The context is left with those lengthscales and their factor.
     """
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     X_train = np.asarray(X_train, dtype=np.float64)
     d = X_train.shape[1]
     ls = np.ones(d) if lengthscales is None else np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy()
@@ -382,12 +402,13 @@ def tune_hyperparms_ard(X_train, y_train, *, sigma=1.0, lengthscales=None, noise
 # than the LML when the model is misspecified.  gpmi_loo gives the per-point held-out predictions and their log
 # probability, gpmi_loo_grad its derivatives w.r.t. (l, sigma, noise_var); the reference has neither.
 # ---------------------------------------------------------------------------------------
-def compute_loo_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None):
+def compute_loo_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None, kernel="rbf"):
     """Leave-one-out log predictive probability, GPML eq. 5.11: the sibling of compute_mar_likelihood, with its argument
     handling (X_test accepted and unused; l a scalar, a 1-element array or a d-vector of per-dimension lengthscales, which
-    do not outlive the call)."""
+    do not outlive the call; kernel: 'rbf' or a Matern)."""
     l, r = split_lengthscale(l)
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     try:
         ctx.fit(X_train, y_train, sigma, l, noise_var, lengthscales=r)
         return np.float64(ctx.loo()[3])
@@ -396,17 +417,19 @@ def compute_loo_likelihood(X_train, X_test, y_train, sigma, l, *, noise_var=NOIS
             ctx.set_lengthscales(None)
 
 
-def loo_and_gradient(X_train, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None):
+def loo_and_gradient(X_train, y_train, sigma, l, *, noise_var=NOISE_VAR, ctx=None, kernel="rbf"):
     """(L_LOO, dL_LOO/dl, dL_LOO/dsigma, dL_LOO/dnoise_var) at (sigma, l, noise_var) with everything resident on the
-    device: the sibling of lml_and_gradient (GPML eqs. 5.11 and 5.13)."""
+    device: the sibling of lml_and_gradient (GPML eqs. 5.11 and 5.13).  kernel: 'rbf' or a Matern."""
     ctx = ctx or default_context()
+    _use_kernel(ctx, kernel)
     ctx.fit(X_train, y_train, sigma, l, noise_var)
     total = ctx.loo()[3]
     dl, ds, dn = ctx.loo_grad()
     return np.float64(total), dl, ds, dn
 
 
-def tune_hyperparms_loo(X_train, y_train, *, sigma=1.0, l=1.0, noise_var=NOISE_VAR, max_iter=100, tol=1e-6, ctx=None):
+def tune_hyperparms_loo(X_train, y_train, *, sigma=1.0, l=1.0, noise_var=NOISE_VAR, max_iter=100, tol=1e-6, ctx=None,
+                        kernel="rbf"):
     """Maximise the leave-one-out log predictive probability over (l, sigma, noise_var) by gradient ascent on their
     logarithms, with the accept / halve / step-carry rule of tune_hyperparms_ard (the same loop).  Per-dimension
     lengthscales the context carries are kept: l is then their common multiplier.
@@ -419,6 +442,7 @@ def tune_hyperparms_loo(X_train, y_train, *, sigma=1.0, l=1.0, noise_var=NOISE_V
     sigma, l, noise_var = scalar(sigma, "sigma"), scalar(l, "l"), scalar(noise_var, "noise_var")
     if not (sigma > 0 and l > 0 and noise_var > 0):
         raise ValueError("l, sigma and noise_var must be positive (the ascent runs on their logarithms)")
+    _use_kernel(ctx, kernel)
     ctx.set_train(X_train, y_train)
 
     def value(th):

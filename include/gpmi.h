@@ -106,18 +106,31 @@ int gpmi_rbf(gpmi_ctx* ctx, const double* a, int64_t N, const double* b, int64_t
 /* The reference's other covariance functions, same layout as gpmi_rbf:
  *   kind 0: RBF_kernel (p0 = sigma, p1 = l)                               GP_regression.py:8-19
  *   kind 1: lin_kernel(a, b, c): np.dot(a - c, b.T - c), p0 = c            GP_regression.py:22-33
- *   kind 2: per_kernel(a, b, (p, l)): exp(-2 sin(pi|a-b|/p)^2 / l^2), d = 1, p0 = p, p1 = l   :36-50 */
+ *   kind 2: per_kernel(a, b, (p, l)): exp(-2 sin(pi|a-b|/p)^2 / l^2), d = 1, p0 = p, p1 = l   :36-50
+ * and the Matern family (Rasmussen & Williams, GPML, section 4.2.1), which the reference does not have:
+ *   kind 4: nu = 1/2,  kind 5: nu = 3/2,  kind 6: nu = 5/2      (p0 = sigma, p1 = l, any d)
+ *   K_ij = sigma^2 P(t) exp(-t),  t = a sqrt(sq_ij),  a = sqrt(2 nu) / |l|,  sq_ij = sum_k (z_ik - z_jk)^2
+ *   P = 1 (nu = 1/2),  1 + t (3/2),  1 + t + t^2 / 3 (5/2)
+ * z = x, or x / r with lengthscales set (gpmi_set_lengthscales).  l == 0 and NaN are refused as for kind 0; a negative
+ * l means |l|.  Evaluation order (only exp itself may differ from a NumPy float64 evaluation in this order):
+ *   1. sq in the pairwise order of kind 0 (NumPy's add.reduce over the middle axis of the (N, d, M) differences);
+ *   2. r = sqrt(sq), correctly rounded;
+ *   3. t = a * r, a = sqrt(2 nu) / |l| computed once on the host in double (sqrt(1.0), sqrt(3.0), sqrt(5.0));
+ *   4. P = 1 + t, or (1 + t) + (t * t) * c3 with c3 the double nearest 1/3 -- one rounding per operation, no FMA;
+ *   5. e = exp(-t), K = sigma^2 * (P * e).
+ * At sq == 0 every factor is exactly 1: the diagonal of K is sigma^2 exactly. */
 int gpmi_cov(gpmi_ctx* ctx, int kind, const double* a, int64_t N, const double* b, int64_t M,
              int64_t d, double p0, double p1, double* out);
 /* Covariance function used by gpmi_factorize / gpmi_predict / gpmi_post_chol from now on
  * (kernel_choice of prediction(), GP_regression.py:125-136).  kind 0 (default) takes sigma and l
- * from gpmi_factorize; kinds 1, 2 take (p0, p1) as above and ignore them. */
+ * from gpmi_factorize; kinds 1, 2 take (p0, p1) as above and ignore them.  Kinds 4, 5, 6 (Matern nu = 1/2, 3/2, 5/2)
+ * take sigma and l from gpmi_factorize and its siblings exactly as kind 0 does, and ignore p0 and p1. */
 int gpmi_set_kernel(gpmi_ctx* ctx, int kind, double p0, double p1);
 /* The composite covariance of the CO2 example (second half):
  *   kind 3: covariance_function(a, b, hyperparms) = kernel_1 + kernel_2 + kernel_3 + kernel_4,
  *           hyperparms = theta_1..theta_11, any d                            CO2_example.py:9-94
  * kernel_4 adds theta_11^2 on row == col whenever the matrix is square (N == M), as the reference
- * does (:58-59).  The *_params forms take the parameters as an array; kinds 0-2 accept
+ * does (:58-59).  The *_params forms take the parameters as an array; kinds 0-2 and 4-6 accept
  * nparams == 2 with (p0, p1) as above. */
 int gpmi_cov_params(gpmi_ctx* ctx, int kind, const double* a, int64_t N, const double* b, int64_t M,
                     int64_t d, const double* params, int nparams, double* out);
@@ -198,12 +211,16 @@ int gpmi_post_sample(gpmi_ctx* ctx, double jitter, const double* Z, int64_t num_
  *   d_sigma = .5 * trace((alpha alpha^T - K_y^-1) @ sigma_grad), sigma_grad = 2 sigma exp(-.5 sqdist/l^2)
  *                                                     tune_hyperparms_regression.py:46-51 (commented out there)
  * with K_y^-1 = inv(L.T) @ inv(L) (:144) formed on the device from the resident L.
- * Squared-exponential kernel only.  With lengthscales set (gpmi_set_lengthscales) sqdist is that of the scaled inputs and
- * d_ell the derivative w.r.t. the common multiplier l. */
+ * Kinds 0, 4, 5 and 6 (another kind -> GPMI_ERR_BAD_ARG).  For the Matern kinds, with H(t) = -(1/t) d(P e^-t)/dt =
+ * e^-t / t (nu = 1/2), e^-t (3/2), (1 + t) e^-t / 3 (5/2):  dK_ij/dl = sigma^2 a^2 H(t_ij) sq_ij / l,  dK/dsigma = 2 K / sigma;
+ * an element with sq_ij == 0 contributes 0 to d_ell (H(t) sq -> 0; duplicate training points are fine for nu = 1/2).
+ * With lengthscales set (gpmi_set_lengthscales) sqdist is that of the scaled inputs and d_ell the derivative w.r.t. the
+ * common multiplier l. */
 int gpmi_lml_grad(gpmi_ctx* ctx, double* d_ell, double* d_sigma);
 /* Per-dimension lengthscales (automatic relevance determination).  The context carries relative lengthscales r_k > 0,
  * k < d (default: all 1), and every squared-exponential covariance it builds becomes
  *   K_ij = sigma^2 exp(-.5 / l^2 * sum_k ((x_ik - x_jk) / r_k)^2)
+ * (a Matern covariance, kinds 4-6, takes the same sum as its sq_ij)
  * -- the effective lengthscale of dimension k is l * r_k, with l the argument every call already takes.  The scaling is
  * done on the inputs: z = x / r, one IEEE division per element on the device, and factorisation, prediction, posterior
  * samples, gpmi_lml_batch, both Laplace classifiers and the gradients read z.  gpmi_rbf / gpmi_cov take their inputs as
@@ -213,11 +230,13 @@ int gpmi_lml_grad(gpmi_ctx* ctx, double* d_ell, double* d_sigma);
  * May be called before or after gpmi_set_train / gpmi_set_test and repeatedly: the raw inputs stay on the device and the
  * scaled copies are regenerated there (d doubles go up).  Drops any resident regression factor, binary Laplace fit and
  * softmax fit, as a new gpmi_set_train does.  A later gpmi_set_train with another d clears the lengthscales; one with the
- * same d keeps them.  Squared-exponential kernel (kind 0) only: a fit with another kind is refused while they are set. */
+ * same d keeps them.  Squared-exponential and Matern kernels (kinds 0, 4, 5, 6): a fit with kind 1, 2 or 3 is refused while
+ * they are set. */
 int gpmi_set_lengthscales(gpmi_ctx* ctx, const double* r, int64_t d);
 /* The gradient of the log marginal likelihood w.r.t. every hyper-parameter at the resident factorisation, with
  * W = alpha alpha^T - K_y^-1 and z = x / r (z = x when no lengthscales are set):
  *   d_r[k]  = .5 * sum_ij W_ij K_ij (z_ik - z_jk)^2 / (l^2 r_k)     (d doubles; d LML / d r_k)
+ *             Matern kinds: .5 * sum_ij W_ij sigma^2 a^2 H(t_ij) (z_ik - z_jk)^2 / r_k, H as at gpmi_lml_grad
  *   d_ell, d_sigma as gpmi_lml_grad (to rounding: another kernel adds them up)
  *   d_noise = .5 * (alpha^T alpha - trace(K_y^-1))                   (d LML / d noise_var)
  * Any output may be NULL.  sum_k r_k d_r[k] == l * d_ell (K depends on l * r_k only).  Refuses what gpmi_lml_grad
@@ -237,8 +256,8 @@ int gpmi_loo(gpmi_ctx* ctx, double* mu, double* var, double* logp, double* loo);
 /* The derivatives of *loo (GPML eq. 5.13) w.r.t. l, sigma and noise_var at the resident factorisation:
  *   d/dtheta = sum_i (alpha_i r_i - .5 (1 + alpha_i^2 / kappa_i) s_i) / kappa_i,
  *   Z = K_y^-1 dK_y/dtheta,  r = Z alpha,  s_i = [Z K_y^-1]_ii
- * with dK_y/dl = K o sqdist / l^3, dK_y/dsigma = 2 K / sigma, dK_y/dnoise_var = I.  Any output may be NULL.  Squared-
- * exponential kernel only: refuses what gpmi_lml_grad refuses; state rules as gpmi_loo.  With lengthscales set, sqdist is
+ * with dK_y/dl = K o sqdist / l^3 (Matern kinds: sigma^2 a^2 H(t) o sqdist / l), dK_y/dsigma = 2 K / sigma,
+ * dK_y/dnoise_var = I.  Any output may be NULL.  Refuses what gpmi_lml_grad refuses; state rules as gpmi_loo.  With lengthscales set, sqdist is
  * that of the scaled inputs and d_ell the derivative w.r.t. the common multiplier l.  The l component takes the diagonal
  * of K_y^-1 (K o sqdist) K_y^-1, a full N x N x N product (2 N^3 flops beside the 2 N^3 / 3 of gpmi_lml_grad), formed
  * NB rows at a time; bitwise reproducible from run to run.  Device memory: DESIGN.md section 4c. */
@@ -428,7 +447,8 @@ int gpmi_dev_rbf_cross(void* stream, const double* Xs_dev, int64_t n, const doub
 /* The same two builds for every covariance function the reference's prediction() serves (GP_regression.py:125-136:
  * 'rbf' / 'lin' / 'per') and for CO2_example.py:66-90's composite -- f4 on the row-block partitioned path.
  * kind / params as gpmi_set_kernel (0: sigma, l; 1: c; 2: period, l -- 1-D inputs) and gpmi_set_kernel_params (3: the
- * 11 hyper-parameters; kernel_4 adds theta_11^2 on the diagonal of a square matrix).  gpmi_dev_cov_cross takes a WINDOW
+ * 11 hyper-parameters; kernel_4 adds theta_11^2 on the diagonal of a square matrix); kinds 4-6 (Matern) take (sigma, l)
+ * as kind 0 does.  gpmi_dev_cov_cross takes a WINDOW
  * of the column inputs that starts at input col0 of the full set; square != 0: the full cross matrix is square (n == N),
  * so the composite kernel's delta term lands on row == col0 + column (CO2_example.py:58-62). */
 int gpmi_dev_cov_rows(void* stream, int kind, const double* params, int nparams, const double* X_dev, int64_t N, int64_t d,
