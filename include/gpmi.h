@@ -456,16 +456,30 @@ int gpmi_dev_cov_rows(void* stream, int kind, const double* params, int nparams,
 int gpmi_dev_cov_cross(void* stream, int kind, const double* params, int nparams, const double* Xs_dev, int64_t n,
                        const double* Xcols_dev, int64_t ncols_real, int64_t d, int64_t col0, int square, int64_t nrows,
                        int64_t ncols, double* out_dev, int64_t ld);
-/* in-place Cholesky of the nb x nb diagonal block (nb multiple of 128);
- * info_dev: int64 on the device, atomically min-ed with col_offset + failing
- * column (initialise to INT64_MAX).  On return the lower triangle holds L; the strict upper triangles of
- * the 16 x 16 tiles on the diagonal hold the transposed inverses of those tiles (storage nothing else reads),
- * which gpmi_dev_trsm_block uses. */
+/* in-place Cholesky of the nb x nb diagonal block (nb multiple of 128, ld even, A_dev 16-byte aligned: a view that
+ * starts on an odd column is refused before anything is launched).
+ * Read: the 16 x 16 tiles on and below the block diagonal, the diagonal tiles whole (the symmetric values the K build
+ * writes there).  The tiles strictly above the block diagonal are never read for the result and may hold anything, NaN
+ * included; the updates inside a block wider than 128 may pass over those that lie inside a 128 x 128 diagonal block.
+ * On return the lower triangle holds L, and the strict upper triangles of the 16 x 16 tiles on the diagonal are
+ * OVERWRITTEN with W^T, W = the inverse of that tile of L (diag(W) = 1 / diag(L) implied), which gpmi_dev_trsm_block,
+ * gpmi_dev_trsv_lt_fused and the vinv forms read back; a block of 128 columns leaves every other tile above the diagonal
+ * as it was.  Under option "panel_fused" 0 (the first-generation 64-column leaves) nothing above the diagonal is the
+ * factor's: such a factor carries NO inverses, and gpmi_dev_trsm_block takes it under the same option only.
+ * info_dev: int64 on the device, atomically min-ed (as 64-bit unsigned) with col_offset + failing column, a pivot that
+ * is negative, zero or NaN (initialise to INT64_MAX).  When several pivots fail, in one 16 x 16 tile or in different
+ * launches of the call, it ends up holding the smallest failing global column; a value already below that stays.  Columns
+ * left of the failing pivot's 16 x 16 tile are those of the clean factor; from that tile on the block is no factor. */
 int gpmi_dev_potrf_block(void* stream, double* A_dev, int64_t ld, int64_t nb,
                          int64_t col_offset, int64_t* info_dev);
 /* X (m x nb, ldx) <- X * L^-T with L the nb x nb lower factor (ldl) AS LEFT BY gpmi_dev_potrf_block / the
- * factorisation (nb multiple of 128: the 16 x 16 diagonal tiles carry their inverses above the diagonal; a
- * copy of the block must be a copy of the whole nb x nb square) */
+ * factorisation (m multiple of 128, nb of 64, ldl and ldx even, both pointers 16-byte aligned).  nb multiple of 128:
+ * the 16 x 16 diagonal tiles carry their inverses above the diagonal, so a copy of the block must be a copy of the
+ * whole nb x nb square.  Read of L: the tiles below the block diagonal and the diagonal tiles whole, nothing above
+ * them.  nb an odd multiple of 64, or option "panel_fused" 0 (required for a factor made under it): the 64-column
+ * substitution leaves, which read the lower triangle only.  L is not written.  One launch or two per 128 columns
+ * (gpmi_dev_set_concurrent) give the same bits, and so do the wave-per-row and lane-per-row forms of the 64-column
+ * leaves (option "trsm_wave"). */
 int gpmi_dev_trsm_block(void* stream, const double* L_dev, int64_t ldl, double* X_dev,
                         int64_t ldx, int64_t m, int64_t nb);
 /* C (M x N, ldc) -= A (M x K, lda) * B (N x K, ldb)^T.  lower != 0: only tiles
