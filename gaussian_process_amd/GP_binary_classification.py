@@ -12,6 +12,9 @@ inverses of the Cholesky factor), which is the traffic this package exists to av
 the likelihood derivatives at the prior sample `f_prior` instead of the current iterate, so W never changes and the
 iteration does not find the mode; its `prediction` also drops the latent variance.  `laplace_fit`, `predict_proba` and
 `predict_label` below are the working forms of those two functions.
+
+`log_q_and_gradient` and `tune_hyperparms_classification` learn sigma and the lengthscales from the gradient of the
+Laplace log marginal likelihood (GPML Algorithm 5.1, gpmi_laplace_grad), which the reference leaves to a grid search.
 """
 from __future__ import annotations
 
@@ -89,3 +92,72 @@ def predict_proba(X_test, *, ctx=None):
 def predict_label(X_test, *, ctx=None):
     """label_function of the latent predictive mean: +1 where f_mean >= 0, else -1."""
     return label_function(predict_latent(X_test, ctx=ctx)[0])
+
+
+# The gradient formula of GPML Algorithm 5.1 holds AT the mode, so whatever distance from it the Newton iteration stops
+# at goes into the gradient: a few 1e-9 relative with laplace_fit's default tol=1e-10, the rounding floor (<= 1e-12) with
+# 1e-13.  The two functions below therefore fit with 1e-13 (one more Newton step at most).
+GRAD_FIT_TOL = 1e-13
+
+
+def log_q_and_gradient(X_train, y_train, sigma, lengthscales, *, ctx=None, tol=GRAD_FIT_TOL, max_iter=100):
+    """(log_q, d_lengthscales, d_sigma): the Laplace approximation of the log marginal likelihood and its derivatives
+    w.r.t. the lengthscales and sigma, the classifier's sibling of lml_and_gradient_ard.
+
+    :param lengthscales: one absolute lengthscale per input dimension -> d_lengthscales is a (d,) array; or a scalar
+                         (the isotropic l, any the context carried are cleared) -> d_lengthscales is one number
+    :param tol, max_iter: of the Newton iteration (see GRAD_FIT_TOL)
+    The context keeps the lengthscales and the fit: predict_proba and ctx.laplace_grad() work on it afterwards.
+    """
+    ctx = default_context() if ctx is None else ctx
+    l, r = split_lengthscale(lengthscales)
+    log_q = ctx.laplace_fit(X_train, y_train, sigma, l, tol=tol, max_iter=max_iter, lengthscales=r)[0]
+    d_r, d_l, d_sigma = ctx.laplace_grad()       # a vector: common l = 1, so d_r is the derivative w.r.t. the lengthscales
+    return np.float64(log_q), (np.float64(d_l) if r is None else d_r), d_sigma
+
+
+def tune_hyperparms_classification(X_train, y_train, *, sigma=1.0, lengthscales=None, max_iter=100, tol=1e-6, ctx=None):
+    """Maximise log_q over (lengthscales, sigma) by gradient ascent on their logarithms: the loop of tune_hyperparms_ard
+    with its step rule -- a trial that lowers log_q is halved, the step length carries over doubled, no parameter moves
+    by more than a factor e -- in the form that never accepts a lower value, so log_q does not decrease along the trace.
+    It stops after max_iter steps or where the norm of the gradient w.r.t. the logarithms is at most tol.  (Not
+    tune_hyperparms_ard's |dlog_q| <= tol max(1, |log_q|): on two overlapping blobs that rule ends the ascent in a curved
+    valley, where the halved steps move log_q by 1e-4 while the gradient norm is still 0.4.)  Every trial is a Newton fit
+    with tol=GRAD_FIT_TOL.  A RuntimeWarning is issued when the ascent ends with a larger gradient norm than tol.
+
+    :param lengthscales: initial per-dimension lengthscales (a scalar: that value for every dimension; default all 1)
+    :return: (lengthscales (d,), sigma, log_q, trace): the parameters reached, their log_q and the log_q of every
+             accepted point, the initial one first.  The context is left with those lengthscales and their fit, so
+             predict_proba follows directly.
+    """
+    import warnings
+
+    from .tune_hyperparms_regression import _log_ascent
+    ctx = default_context() if ctx is None else ctx
+    X_train = np.asarray(X_train, dtype=np.float64)
+    d = X_train.shape[1]
+    ls = np.ones(d) if lengthscales is None else np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy()
+    if ls.shape[0] == 1 and d > 1:
+        ls = np.full(d, ls[0])
+    if ls.shape[0] != d or not np.all(np.isfinite(ls)) or np.any(ls <= 0):
+        raise ValueError("lengthscales must be %d finite positive numbers" % d)
+    if not sigma > 0:
+        raise ValueError("sigma must be positive (the ascent runs on its logarithm)")
+
+    def value(th):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)      # a trial point's unconverged fit is just a poor trial
+            return float(ctx.laplace_fit(X_train, y_train, np.exp(th[d]), 1.0, tol=GRAD_FIT_TOL,
+                                         lengthscales=np.exp(th[:d]))[0])
+
+    def gradient():
+        d_r, _, d_sigma = ctx.laplace_grad()
+        return np.concatenate([d_r, [d_sigma]])
+
+    theta, log_q, trace = _log_ascent(value, gradient, np.log(np.concatenate([ls, [float(sigma)]])), max_iter, tol,
+                                      monotone=True, gtol=tol)
+    gnorm = float(np.linalg.norm(gradient() * np.exp(theta)))
+    if not gnorm <= tol:
+        warnings.warn("tune_hyperparms_classification: stopped after %d of at most %d steps with gradient norm %.3g "
+                      "(tol=%g)" % (len(trace) - 1, max_iter, gnorm, tol), RuntimeWarning, stacklevel=2)
+    return np.exp(theta[:d]), float(np.exp(theta[d])), np.float64(log_q), np.asarray(trace)

@@ -71,6 +71,7 @@ SIGNATURES = {
     "gpmi_lml_batch": [_vp, _dp, _i64, _dp, C.POINTER(C.c_int)],
     "gpmi_laplace_fit": [_vp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp],
     "gpmi_laplace_predict_resident": [_vp, _dp, _dp, _dp],
+    "gpmi_laplace_grad": [_vp, _dp, _dp, _dp],
     "gpmi_softmax_fit": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int),
                          C.POINTER(C.c_int), _dp],
     "gpmi_softmax_predict_resident": [_vp, _dp, _dp, _i64, _dp, _dp],

@@ -653,6 +653,12 @@ int gpmi_laplace_predict_resident(gpmi_ctx* c, double* f_mean, double* f_var, do
     return laplace_predict_impl(c, f_mean, f_var, prob);
 }
 
+int gpmi_laplace_grad(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) {
+    if (!c) return fail_arg("gpmi_laplace_grad: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return laplace_grad_impl(c, d_r, d_ell, d_sigma);
+}
+
 // Multi-class GP classification, GPML Algorithms 3.3 / 3.4 with the softmax likelihood (softmax.hip)
 int gpmi_softmax_fit(gpmi_ctx* c, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
                      int* iters, int* converged, double* f_hat) {

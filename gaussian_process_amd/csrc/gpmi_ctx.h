@@ -293,6 +293,10 @@ hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out);
 int fail_gave_up(const char* api);
 // regress.hip: the regression calls of include/gpmi.h on the resident factorisation, behind the shims' pointer checks
 int alpha_impl(gpmi_ctx* c, double* alpha_out);
+// The body of the regression gradients' front, for any factor resident in A: the slot's timer reset, U, (want_kn) Kn and
+// vec made large enough, then inside a span of that slot, which it opens: (alpha_out not null) alpha = L^-T m,
+// U = L^-T by the TRSM sweep on the identity and (want_kn) Kn = -U U^T on the lower tiles
+int factor_inverse_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span);
 int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
 int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma);
 int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
@@ -313,6 +317,7 @@ inline Tuning resident_tuning(const gpmi_ctx* c) {
 int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat);
 int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob);
+int laplace_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma);
 // The Newton skeleton of both classifiers (laplace.hip).  classifier_fit_check: the arguments both take, under the
 // caller's API name; `own` is the text of a failed check of the caller's own arguments (or null), reported at its place
 // behind the kernel check.  classifier_fit_begin: the resident fit goes, A and the hyper-parameters are set up, the

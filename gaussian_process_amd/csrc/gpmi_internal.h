@@ -207,6 +207,11 @@ struct GradArdArgs {
     int family = 0;           // cov_family of the kernel: the "x" of the sums is then H(t) and sums[width + 1] takes K / sigma^2
     double* partial;          // (width + 3) * grad_ard_blocks doubles, component-major
     double* sums;             // (width + 3) * grad_ard_launches doubles
+    // The binary classifier's gradient (gpmi_laplace_grad; family 0 only): with lap_s set, alpha is a, Kn is -B^-1 and
+    // the weight is a_i a_j + s_i s_j Kn_ij + z_i g_j + z_j g_i; there is no noise sum (its slot holds 0)
+    const double* lap_s = nullptr;
+    const double* lap_z = nullptr;
+    const double* lap_g = nullptr;
 };
 int64_t grad_ard_blocks(const GradArdArgs& a);
 int64_t grad_ard_width(const GradArdArgs& a);

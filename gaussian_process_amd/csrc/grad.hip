@@ -189,9 +189,22 @@ struct ArdDev {
     double* partial;
     int64_t nblk;
 };
+// The binary classifier's variant (gpmi_laplace_grad): alpha is a, Kn is -B^-1 and the weight of element (i, j) is
+//     w = a_i a_j + s_i s_j Kn_ij + z_i g_j + z_j g_i
+// -- four more vector loads per row and per column, two more multiplications and two more FMAs per element, no noise sum
+// (its slot is written 0).
+// A separate instantiation (LAP, family 0 only) with its own argument block: the regression instantiations are the code
+// they were.
+struct ArdLapDev : ArdDev {
+    const double* s;
+    const double* z;
+    const double* g;
+};
+template <bool LAP> struct ArdDevOf { typedef ArdDev type; };
+template <> struct ArdDevOf<true> { typedef ArdLapDev type; };
 
-template <int DC, bool LDS, int F>
-__global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
+template <int DC, bool LDS, int F, bool LAP = false>
+__global__ __launch_bounds__(256) void grad_ard_kernel(const typename ArdDevOf<LAP>::type p) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[4][DC + 3];
     const int s = blockIdx.x;
@@ -225,6 +238,8 @@ __global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
         if (gr >= p.n) break;                                    // wave-uniform
         const double ar_ = p.alpha[gr];
         const double* kp = p.Kn + gr * p.ld + gc;
+        double sr_ = 0.0, zr_ = 0.0, gr_ = 0.0;
+        if constexpr (LAP) { sr_ = p.s[gr]; zr_ = p.z[gr]; gr_ = p.g[gr]; }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {                            // the thread's two columns, one after the other
             const int64_t g = gc + 64 * c;
@@ -260,9 +275,20 @@ __global__ __launch_bounds__(256) void grad_ard_kernel(const ArdDev p) {
                 }
             }
             // Kn holds -K_y^-1, valid on and below the diagonal only
-            double w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
-            if (g == gr) acc_n += w;
-            else w += w;
+            double w;
+            if constexpr (LAP) {
+                w = 0.0;
+                if (in && g <= gr) {
+                    w = fma(ar_, p.alpha[g], (sr_ * p.s[g]) * kp[64 * c]);
+                    w = fma(zr_, p.g[g], w);
+                    w = fma(p.z[g], gr_, w);
+                }
+                if (g != gr) w += w;
+            } else {
+                w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
+                if (g == gr) acc_n += w;
+                else w += w;
+            }
             double wx, ws;                                       // the weight of the lengthscale sums and of sigma's
             if constexpr (F == 0) {
                 wx = ws = w * exp(p.coef * sq);
@@ -570,6 +596,19 @@ static void grad_ard_go(hipStream_t s, const ArdDev& p) {
     hipLaunchKernelGGL((grad_ard_kernel<DC, true, F>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
 }
 
+template <int DC>
+static void laplace_ard_go(hipStream_t s, const ArdLapDev& p) {
+    hipLaunchKernelGGL((grad_ard_kernel<DC, true, 0, true>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
+}
+
+static void laplace_ard_launch(hipStream_t s, const ArdLapDev& p, int64_t d, int w) {
+    if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, 0, true>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
+    else if (w == 4) laplace_ard_go<4>(s, p);
+    else if (w == 8) laplace_ard_go<8>(s, p);
+    else if (w == 16) laplace_ard_go<16>(s, p);
+    else laplace_ard_go<32>(s, p);
+}
+
 template <int F>
 static void grad_ard_launch(hipStream_t s, const ArdDev& p, int64_t d, int w) {
     if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, F>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
@@ -582,14 +621,18 @@ static void grad_ard_launch(hipStream_t s, const ArdDev& p, int64_t d, int w) {
 hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
     if (a.n <= 0 || a.d <= 0) return hipSuccess;
     if (a.family < 0 || a.family > 3) return hipErrorInvalidValue;
-    ArdDev p;
+    const bool lap = a.lap_s != nullptr;
+    if (lap && (a.family != 0 || !a.lap_z || !a.lap_g)) return hipErrorInvalidValue;
+    ArdLapDev p;
     p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld; p.coef = a.coef;
     p.partial = a.partial; p.nblk = grad_ard_blocks(a);
+    p.s = a.lap_s; p.z = a.lap_z; p.g = a.lap_g;
     const int w = (int)grad_ard_width(a);
     const int64_t nl = grad_ard_launches(a);
     for (int64_t q = 0; q < nl; ++q) {       // d > 32: every launch recomputes the whole squared distance and reads Kn again
         p.k0 = (int)(q * GRAD_MAXD);
-        switch (a.family) {
+        if (lap) laplace_ard_launch(s, p, a.d, w);
+        else switch (a.family) {
             case 0: grad_ard_launch<0>(s, p, a.d, w); break;
             case 1: grad_ard_launch<1>(s, p, a.d, w); break;
             case 2: grad_ard_launch<2>(s, p, a.d, w); break;

@@ -13,6 +13,8 @@
 //   laplace_update_kernel       a <- b - W^1/2 x (keeping the previous a, f for step halving)
 //   laplace_rows_kernel         prediction: f* = K(X*, X) grad, then the rows are scaled by W^1/2 in place
 //   laplace_quad_kernel         prediction: V* = sigma^2 - |v|^2 and pi* = int expit(z) N(z | f*, V*) dz
+//   laplace_s2_kernel           gradient: s2 = -(1 - [B^-1]_ii) (1 - 2 pi) / 2 from kappa and f^
+//   laplace_z_kernel            gradient: z = s2 + s o (Kn t) from the tile partials
 // Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
 #include "gpmi_ctx.h"
 #include "lap_dev.h"
@@ -261,6 +263,25 @@ __global__ __launch_bounds__(VEC_THREADS) void laplace_quad_kernel(int64_t n, co
     prob[i] = acc;
 }
 
+// s2_i = -(1 - kappa_i) (1 - 2 pi_i) / 2 with pi = expit(f^): half the diagonal of Sigma = (K^-1 + W)^-1 times the third
+// derivative of log p (Sigma_ii W_i = 1 - [B^-1]_ii and the logistic's third derivative is -W (1 - 2 pi): W cancels, so
+// saturated points lose nothing); 0 past N
+__global__ __launch_bounds__(VEC_THREADS) void laplace_s2_kernel(int64_t N, int64_t Np, const double* __restrict__ kappa,
+                                                                 const double* __restrict__ f, double* __restrict__ s2) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    s2[i] = i < N ? -0.5 * ((1.0 - kappa[i]) * (1.0 - 2.0 * expit(f[i]))) : 0.0;
+}
+
+// z = s2 + s o (Kn t) from the tile partials of Kn t (Kn = -B^-1, t = s o (K s2): z = s2 - R K s2), 0 past N
+__global__ __launch_bounds__(VEC_THREADS) void laplace_z_kernel(const double* __restrict__ part, int64_t nt, int64_t N,
+                                                                int64_t Np, const double* __restrict__ s,
+                                                                const double* __restrict__ s2, double* __restrict__ z) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    z[i] = i < N ? fma(s[i], slot_sum(part, nt, i), s2[i]) : 0.0;
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
 
 }  // namespace
@@ -344,16 +365,17 @@ static NewtonVecs newton_vecs(gpmi_ctx* c) {
                       L + LV_B * Np};
 }
 
-static hipError_t launch_symv(gpmi_ctx* c, bool scale, const double* x) {
+// over the lower tiles of M (Np x Np, leading dimension ld): the freshly built K in A during the fit
+static hipError_t launch_symv(gpmi_ctx* c, double* M, int64_t ld, bool scale, const double* x) {
     const int64_t nt = c->Np / TILE;
     const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
     double* s = c->lap.as<double>() + LV_S * c->Np;
     if (scale)
-        hipLaunchKernelGGL(laplace_symv_kernel<true>, dim3(tiles), dim3(SYMV_THREADS), 0, c->stream, c->A.as<double>(),
-                           c->ldA, nt, c->N, x, s, c->lap_part.as<double>());
+        hipLaunchKernelGGL(laplace_symv_kernel<true>, dim3(tiles), dim3(SYMV_THREADS), 0, c->stream, M, ld, nt, c->N, x, s,
+                           c->lap_part.as<double>());
     else
-        hipLaunchKernelGGL(laplace_symv_kernel<false>, dim3(tiles), dim3(SYMV_THREADS), 0, c->stream, c->A.as<double>(),
-                           c->ldA, nt, c->N, x, s, c->lap_part.as<double>());
+        hipLaunchKernelGGL(laplace_symv_kernel<false>, dim3(tiles), dim3(SYMV_THREADS), 0, c->stream, M, ld, nt, c->N, x, s,
+                           c->lap_part.as<double>());
     return hipGetLastError();
 }
 
@@ -401,7 +423,7 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
     int it = 0;
     for (;;) {
         HIP_TRY(launch_rbf(st, r));                                   // 1. K
-        HIP_TRY(launch_symv(c, false, v.a));                          // 2. f = K a
+        HIP_TRY(launch_symv(c, A, c->ldA, false, v.a));                          // 2. f = K a
         if ((rc = evaluate(0)) != GPMI_OK) return rc;                 // 3.
         if (have_prev) {                                              // 4.
             for (int halvings = 0;; ++halvings) {
@@ -410,7 +432,7 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
                 if ((rc = evaluate(1)) != GPMI_OK) return rc;
             }
         }
-        HIP_TRY(launch_symv(c, true, v.b));                           // 5. u = K b, K <- B
+        HIP_TRY(launch_symv(c, A, c->ldA, true, v.b));                           // 5. u = K b, K <- B
         hipLaunchKernelGGL(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
                            (const double*)c->lap_part.as<double>(), nt, N, Np, (const double*)v.s, L + LV_C * Np);
         HIP_TRY(hipGetLastError());
@@ -476,6 +498,67 @@ int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* pro
     if (prob) HIP_TRY(hipMemcpyAsync(prob, o + 4 * np_, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
+    return GPMI_OK;
+}
+
+// The gradient of log q at the resident fit (GPML Algorithm 5.1; include/gpmi.h has the formulas).  U = L^-T, kappa_i =
+// [B^-1]_ii from U's rows and Kn = -B^-1 = -U U^T as the regression gradients form them; K rebuilt into U's buffer, which
+// is dead by then, for t = s o (K s2); z = s2 + s o (Kn t); then the fused trace of grad.hip with the classifier's weight.
+// Reads L, a, f^, s and grad only; its vectors live in loov, the tile partials in lap_part (scratch of the fit).
+int laplace_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) {
+    if (!c->res.laplace()) return fail_arg("gpmi_laplace_grad: no Laplace fit resident (call gpmi_laplace_fit)");
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    hipStream_t st = c->stream;
+    const int64_t N = c->N, Np = c->Np, nt = Np / TILE, ld = c->ldA;
+    HIP_TRY(c->loov.ensure((size_t)(4 * Np + 8) * 8));
+    HIP_TRY(c->lap_part.ensure((size_t)nt * nt * TILE * 8));
+    size_t sp = 0;
+    int rc = factor_inverse_front(c, GPMI_T_GRAD, true, nullptr, &sp);
+    if (rc) return rc;
+    double* kappa = c->loov.as<double>();
+    double *s2 = kappa + Np, *t = s2 + Np, *z = t + Np;
+    double *Kb = c->U.as<double>(), *Kn = c->Kn.as<double>();
+    const double* L = c->lap.as<double>();
+    const double *a = L + LV_A * Np, *f = L + LV_F * Np, *s = L + LV_S * Np, *g = L + LV_G * Np;
+    HIP_TRY(launch_loo_kappa(st, Kb, ld, N, kappa));                 // U is still L^-T here
+    hipLaunchKernelGGL(laplace_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, (const double*)kappa, f, s2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_rbf(st, rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, Kb, ld)));
+    HIP_TRY(launch_symv(c, Kb, ld, false, s2));
+    hipLaunchKernelGGL(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
+                       (const double*)c->lap_part.as<double>(), nt, N, Np, s, t);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_symv(c, Kn, ld, false, t));
+    hipLaunchKernelGGL(laplace_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
+                       (const double*)c->lap_part.as<double>(), nt, N, Np, s, (const double*)s2, z);
+    HIP_TRY(hipGetLastError());
+
+    GradArdArgs ga;
+    ga.Z = c->x_train(); ga.n = N; ga.d = c->d;
+    ga.alpha = a; ga.Kn = Kn; ga.ld = ld; ga.coef = c->coef;
+    ga.family = 0;
+    ga.lap_s = s; ga.lap_z = z; ga.lap_g = g;
+    const int64_t nblk = grad_ard_blocks(ga), nl = grad_ard_launches(ga), w = grad_ard_width(ga);
+    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
+    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
+    ga.partial = c->gpart.as<double>();
+    ga.sums = c->gsum.as<double>();
+    HIP_TRY(launch_grad_ard(st, ga));
+    c->span_end(sp);
+    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
+    HIP_TRY(hipMemcpyAsync(sums.data(), ga.sums, sums.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+    // the plain sums of lml_grad_ard_impl, with its factors: sum w K/sigma^2 e_k^2 per dimension, then the l and sigma sums
+    const double l2 = c->ell * c->ell;
+    if (d_r)
+        for (int64_t k = 0; k < c->d; ++k) {
+            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
+            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
+        }
+    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
+    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
     return GPMI_OK;
 }
 

@@ -103,18 +103,23 @@ int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
 // The front of both LML gradients and of the leave-one-out calls: the resident factorisation and -- rbf_only not null --
 // its kernel (kinds 0, 4, 5, 6: the stationary ones the gradient kernels have a family for) checked with the caller's own texts, the slot's timer reset, and inside a span of that slot, which it opens:
 // alpha = L^-T m (a5; solve_epilogue reads the backward solve's give-up word), U = L^-T by the TRSM sweep on the identity
-// and -- want_kn -- Kn = -U U^T on the lower tiles.
+// and -- want_kn -- Kn = -U U^T on the lower tiles.  Everything behind the two checks is factor_inverse_front, which the
+// binary classifier's gradient (laplace.hip) runs on its own factor without the backward solve.
 static int grad_front(gpmi_ctx* c, const char* not_resident, const char* rbf_only, int slot, bool want_kn, double** alpha_out,
                       size_t* span) {
     if (!c->res.regression()) return fail_arg(not_resident);
     if (rbf_only && !cov_stationary(c->kind)) return fail_arg(rbf_only);
+    return factor_inverse_front(c, slot, want_kn, alpha_out, span);
+}
+
+int factor_inverse_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span) {
     c->timers_reset({slot});
     const int64_t Np = c->Np, ld = c->ldA;
     HIP_TRY(c->U.ensure((size_t)Np * ld * 8));
     if (want_kn) HIP_TRY(c->Kn.ensure((size_t)Np * ld * 8));
     HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
     *span = c->span_begin(slot);
-    HIP_TRY(backward_solve_resident(c, c->vec.as<double>(), alpha_out));
+    if (alpha_out) HIP_TRY(backward_solve_resident(c, c->vec.as<double>(), alpha_out));
     HIP_TRY(inverse_transposed(c, c->A.as<double>(), ld, Np, c->U.as<double>(), ld));
     if (want_kn) HIP_TRY(neg_gram_lower(c, c->U.as<double>(), c->Kn.as<double>(), ld, Np));
     return GPMI_OK;

@@ -318,7 +318,7 @@ def lml_and_gradient_ard(X_train, y_train, sigma, lengthscales, *, noise_var=NOI
     return np.float64(lml), d_r, d_sigma, d_noise
 
 
-def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=False):
+def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=False, gtol=None):
     """The accept / halve / step-carry ascent on the logarithms of positive parameters that tune_hyperparms_ard,
     tune_hyperparms_loo and tune_hyperparms_sparse share.  value(theta) -> the criterion at exp(theta), leaving its
     factorisation resident (-inf where K + sI is not positive definite); gradient() -> its derivatives w.r.t. exp(theta)
@@ -326,6 +326,9 @@ def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=Fals
     coordinates (the inducing inputs) whose entries of gradient() are used as they are; None: all of them.  monotone: a
     trial that is still lower after the last halving is not accepted -- the ascent stops where it stands -- so the values
     of the accepted points never decrease (without it the last trial is accepted, as the two older tuners always did).
+    gtol: stop where the Euclidean norm of the gradient w.r.t. theta is at most gtol INSTEAD of where the value moved by at
+    most tol max(1, |value|) (tune_hyperparms_classification: in a curved valley the halved steps move the value by less
+    than that long before the gradient is small).
     -> (theta reached, its value, the values of every accepted point, the initial one first)."""
     cur = value(theta)
     if not np.isfinite(cur):
@@ -336,7 +339,7 @@ def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=Fals
         jac = np.exp(theta) if n_log is None else np.concatenate([np.exp(theta[:n_log]), np.ones(theta.size - n_log)])
         g = gradient() * jac
         gmax = float(np.max(np.abs(g)))
-        if not np.isfinite(gmax) or gmax == 0.0:
+        if not np.isfinite(gmax) or gmax == 0.0 or (gtol is not None and float(np.linalg.norm(g)) <= gtol):
             break
         cap = ARD_MAX_LOG_STEP / gmax
         step = cap if step is None else min(step, cap)
@@ -354,7 +357,7 @@ def _log_ascent(value, gradient, theta, max_iter, tol, n_log=None, monotone=Fals
         cur = new
         trace.append(cur)
         step *= 2.0
-        if delta <= tol * max(1.0, abs(cur)):
+        if gtol is None and delta <= tol * max(1.0, abs(cur)):
             break
     return theta, cur, trace
 

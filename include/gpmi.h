@@ -299,6 +299,19 @@ int gpmi_laplace_fit(gpmi_ctx* ctx, double sigma, double ell, double tol, int ma
  *   prob = int expit(z) N(z | f_mean, f_var) dz     (composite trapezoid rule, error below 1e-12)
  * each n doubles or NULL. */
 int gpmi_laplace_predict_resident(gpmi_ctx* ctx, double* f_mean, double* f_var, double* prob);
+/* Gradient of log_q at the resident Laplace fit (GPML Algorithm 5.1, logistic likelihood) w.r.t. the relative
+ * lengthscales of gpmi_set_lengthscales (d_r: d doubles, all r_k = 1 when none are set), the common lengthscale and
+ * sigma, with the conventions of gpmi_lml_grad_ard; any pointer may be NULL (K has no noise term).  With pi = expit(f^),
+ * W = pi (1 - pi), s = W^1/2, g = grad(f^), a = K^-1 f^ (the fit's last iterate; = g at the mode), B = L L^T:
+ *   dlog_q/dtheta = sum_ik dK_ik/dtheta [ (a_i a_k - R_ik) / 2 + (z_i g_k + z_k g_i) / 2 ],   R = diag(s) B^-1 diag(s),
+ *   z = s2 - R K s2,   s2_i = -(1 - [B^-1]_ii) (1 - 2 pi_i) / 2
+ * (z^T dK g is the implicit term s2^T (I - K R) dK g of Algorithm 5.1).  The formula holds AT the mode: the result
+ * carries the fit's distance from it, so fit with tol = 1e-13 (the default 1e-10 leaves up to a few 1e-9 relative).
+ * U = L^-T, -B^-1 = -U U^T and [B^-1]_ii as in gpmi_lml_grad / gpmi_loo, K rebuilt into U's buffer, then one fused
+ * pass over the lower tiles for all d + 2 derivatives.  Only reads the fit: it stays resident and
+ * gpmi_laplace_predict_resident returns the same bits afterwards.  GPMI_ERR_BAD_ARG ("no Laplace fit resident") without
+ * one.  The call runs no backward solve, so there is no give-up word to report.  Time: the GPMI_T_GRAD slot. */
+int gpmi_laplace_grad(gpmi_ctx* ctx, double* d_r, double* d_ell, double* d_sigma);
 
 /* Multi-class GP classification by the Laplace approximation: GPML Algorithm 3.3 (Newton iteration for the mode, softmax
  * likelihood, one latent function per class, all with the same squared-exponential prior K = sigma^2 exp(-.5 / l^2
