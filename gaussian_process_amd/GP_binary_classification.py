@@ -130,12 +130,18 @@ def tune_hyperparms_classification(X_train, y_train, *, sigma=1.0, lengthscales=
              accepted point, the initial one first.  The context is left with those lengthscales and their fit, so
              predict_proba follows directly.
     """
+    ctx = default_context() if ctx is None else ctx
+    return _tune_classifier(lambda sigma, ls: ctx.laplace_fit(X_train, y_train, sigma, 1.0, tol=GRAD_FIT_TOL, lengthscales=ls)[0],
+                            ctx.laplace_grad, X_train, sigma, lengthscales, max_iter, tol)
+
+
+def _tune_classifier(fit, grad, X_train, sigma, lengthscales, max_iter, tol):
+    """The ascent of tune_hyperparms_classification, shared with GP_multi_classification: fit(sigma, lengthscales) fits
+    with common l = 1 and returns log_q, grad() returns (d_r, d_l, d_sigma) of the resident fit."""
     import warnings
 
     from .tune_hyperparms_regression import _log_ascent
-    ctx = default_context() if ctx is None else ctx
-    X_train = np.asarray(X_train, dtype=np.float64)
-    d = X_train.shape[1]
+    d = np.asarray(X_train).shape[1]
     ls = np.ones(d) if lengthscales is None else np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy()
     if ls.shape[0] == 1 and d > 1:
         ls = np.full(d, ls[0])
@@ -147,11 +153,10 @@ def tune_hyperparms_classification(X_train, y_train, *, sigma=1.0, lengthscales=
     def value(th):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)      # a trial point's unconverged fit is just a poor trial
-            return float(ctx.laplace_fit(X_train, y_train, np.exp(th[d]), 1.0, tol=GRAD_FIT_TOL,
-                                         lengthscales=np.exp(th[:d]))[0])
+            return float(fit(np.exp(th[d]), np.exp(th[:d])))
 
     def gradient():
-        d_r, _, d_sigma = ctx.laplace_grad()
+        d_r, _, d_sigma = grad()
         return np.concatenate([d_r, [d_sigma]])
 
     theta, log_q, trace = _log_ascent(value, gradient, np.log(np.concatenate([ls, [float(sigma)]])), max_iter, tol,
@@ -159,5 +164,5 @@ def tune_hyperparms_classification(X_train, y_train, *, sigma=1.0, lengthscales=
     gnorm = float(np.linalg.norm(gradient() * np.exp(theta)))
     if not gnorm <= tol:
         warnings.warn("tune_hyperparms_classification: stopped after %d of at most %d steps with gradient norm %.3g "
-                      "(tol=%g)" % (len(trace) - 1, max_iter, gnorm, tol), RuntimeWarning, stacklevel=2)
+                      "(tol=%g)" % (len(trace) - 1, max_iter, gnorm, tol), RuntimeWarning, stacklevel=3)
     return np.exp(theta[:d]), float(np.exp(theta[d])), np.float64(log_q), np.asarray(trace)

@@ -11,6 +11,9 @@ literal 60).  Its `model_training` / `model_training2` and `prediction` are not 
 block-diagonal kernel matrix and explicit inverses on the host, `model_training2` adds pi where the gradient has - pi,
 and `prediction` returns whether one test point was labelled correctly.  `laplace_fit`, `predict_latent`, `predict_proba`
 and `predict_label` below are the working forms.
+
+`log_q_and_gradient` and `tune_hyperparms_classification` learn sigma and the lengthscales from the gradient of the
+Laplace log marginal likelihood (gpmi_softmax_grad), where the reference hard-codes them.
 """
 from __future__ import annotations
 
@@ -88,3 +91,47 @@ def predict_proba(X_test, *, n_samples=1000, seed=0, normals=None, ctx=None):
 def predict_label(X_test, *, ctx=None):
     """argmax over the classes of the latent predictive mean (the reference's `prediction`)."""
     return np.argmax(predict_latent(X_test, ctx=ctx)[0], axis=1)
+
+
+# The gradient formula holds AT the mode (see GP_binary_classification.GRAD_FIT_TOL): the two functions below fit with
+# 1e-13, one more Newton step at most than the default.
+GRAD_FIT_TOL = 1e-13
+
+
+def log_q_and_gradient(X_train, labels, sigma, lengthscales, *, n_classes=None, ctx=None, tol=GRAD_FIT_TOL, max_iter=100):
+    """(log_q, d_lengthscales, d_sigma): the Laplace approximation of the log marginal likelihood of the softmax
+    classifier and its derivatives w.r.t. the lengthscales and sigma of the kernel the classes share
+    (gpmi_softmax_grad), the multi-class sibling of GP_binary_classification.log_q_and_gradient.
+
+    :param lengthscales: one absolute lengthscale per input dimension -> d_lengthscales is a (d,) array; or a scalar
+                         (the isotropic l, any the context carried are cleared) -> d_lengthscales is one number
+    :param tol, max_iter: of the Newton iteration (see GRAD_FIT_TOL)
+    The context keeps the lengthscales and the fit: predict_proba and ctx.softmax_grad() work on it afterwards.
+    """
+    labels, n_classes = softmax_labels(labels, n_classes)
+    ctx = default_context() if ctx is None else ctx
+    l, r = split_lengthscale(lengthscales)
+    log_q = ctx.softmax_fit(X_train, labels, n_classes, sigma, l, tol=tol, max_iter=max_iter, lengthscales=r)[0]
+    d_r, d_l, d_sigma = ctx.softmax_grad()       # a vector: common l = 1, so d_r is the derivative w.r.t. the lengthscales
+    return np.float64(log_q), (np.float64(d_l) if r is None else d_r), d_sigma
+
+
+def tune_hyperparms_classification(X_train, labels, *, n_classes=None, sigma=1.0, lengthscales=None, max_iter=100, tol=1e-6,
+                                   ctx=None):
+    """Maximise log_q over (lengthscales, sigma) by gradient ascent on their logarithms, exactly as
+    GP_binary_classification.tune_hyperparms_classification does for the binary classifier: a trial that lowers log_q
+    is halved and never accepted, so log_q does not decrease along the trace; the ascent stops after max_iter steps or
+    where the norm of the gradient w.r.t. the logarithms is at most tol.  Every trial is a Newton fit with
+    tol=GRAD_FIT_TOL.  A RuntimeWarning is issued when the ascent ends with a larger gradient norm than tol.
+
+    :param lengthscales: initial per-dimension lengthscales (a scalar: that value for every dimension; default all 1)
+    :return: (lengthscales (d,), sigma, log_q, trace): the parameters reached, their log_q and the log_q of every
+             accepted point, the initial one first.  The context is left with those lengthscales and their fit, so
+             predict_proba follows directly.
+    """
+    from .GP_binary_classification import _tune_classifier
+    labels, n_classes = softmax_labels(labels, n_classes)
+    ctx = default_context() if ctx is None else ctx
+    return _tune_classifier(lambda sigma, ls: ctx.softmax_fit(X_train, labels, n_classes, sigma, 1.0, tol=GRAD_FIT_TOL,
+                                                              lengthscales=ls)[0],
+                            ctx.softmax_grad, X_train, sigma, lengthscales, max_iter, tol)

@@ -75,6 +75,7 @@ SIGNATURES = {
     "gpmi_softmax_fit": [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_int),
                          C.POINTER(C.c_int), _dp],
     "gpmi_softmax_predict_resident": [_vp, _dp, _dp, _i64, _dp, _dp],
+    "gpmi_softmax_grad": [_vp, _dp, _dp, _dp],
     "gpmi_sparse_fit": [_vp, _dp, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(_i64)],
     "gpmi_sparse_predict_resident": [_vp, _dp, _dp, C.c_int],
     "gpmi_sparse_get": [_vp, _dp, _dp],

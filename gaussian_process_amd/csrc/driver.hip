@@ -458,4 +458,16 @@ hipError_t neg_gram_lower(gpmi_ctx* c, const double* V, double* Out, int64_t ld,
     return e;
 }
 
+// Out -= V V^T on the lower tiles for a dense V: every row block runs over all n columns of V, and nothing is zeroed
+// (the softmax gradient adds one such product per class)
+hipError_t neg_gram_lower_dense(gpmi_ctx* c, const double* V, double* Out, int64_t ld, int64_t n) {
+    hipError_t e = hipSuccess;
+    const int64_t NB = c->block(n);
+    for (int64_t r0 = 0; r0 < n && e == hipSuccess; r0 += NB) {
+        const int64_t nb = std::min<int64_t>(NB, n - r0);
+        e = launch_gemm_nt(c->stream, gemm_minus_lower(Out + r0 * ld, ld, V + r0 * ld, ld, V, ld, nb, r0 + nb, n, r0));
+    }
+    return e;
+}
+
 }  // namespace gpmi

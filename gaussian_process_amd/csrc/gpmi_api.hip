@@ -675,6 +675,12 @@ int gpmi_softmax_predict_resident(gpmi_ctx* c, double* mu, double* cov, int64_t 
     return softmax_predict_impl(c, mu, cov, n_samples, normals, prob);
 }
 
+int gpmi_softmax_grad(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) {
+    if (!c) return fail_arg("gpmi_softmax_grad: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    return softmax_grad_impl(c, d_r, d_ell, d_sigma);
+}
+
 int gpmi_sparse_fit(gpmi_ctx* c, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,
                     int method, double* value, int64_t* bad_pivot) {
     if (!c || !Z) return fail_arg("gpmi_sparse_fit: null argument");

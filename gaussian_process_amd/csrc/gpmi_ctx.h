@@ -264,6 +264,8 @@ hipError_t solve_sweep_factor(gpmi_ctx* c, const double* L, int64_t ld, int64_t 
 // lower tiles for such a V, one launch per row block of c->block(n) rows
 hipError_t inverse_transposed(gpmi_ctx* c, const double* F, int64_t ldf, int64_t n, double* V, int64_t ldv);
 hipError_t neg_gram_lower(gpmi_ctx* c, const double* V, double* Out, int64_t ld, int64_t n);
+// Out -= V V^T on the lower tiles for a dense V (the caller zeroes Out before the first of a sum), the same row blocks
+hipError_t neg_gram_lower_dense(gpmi_ctx* c, const double* V, double* Out, int64_t ld, int64_t n);
 // The kernel-matrix launches of a context, ready for launch_rbf.  rbf_cross: rows row0 .. row0 + nrows of K(A, B) for point
 // sets of nA and nB points with boxes ba and bb, ncols columns, nothing on the diagonal; the delta term of the composite
 // kernel counts as on a square matrix only for the test set against a training set of the same size.  rbf_sym: the lower
@@ -290,6 +292,8 @@ hipError_t backward_solve_fused(gpmi_ctx* c, double* b, double* xout);
 // x = L^-T m for the m of the y row, through the fused solve or the plain one as the resident factor asks: x2 holds 2 Np
 // doubles, *x_out says where in it the solution lies; fail_gave_up: the status of a one-launch solve whose give-up word is set
 hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out);
+// the same for a right-hand side the caller has put into x2[0 .. Np) (zero past N), which leaves the y row alone
+hipError_t backward_solve_rhs(gpmi_ctx* c, double* x2, double** x_out);
 int fail_gave_up(const char* api);
 // regress.hip: the regression calls of include/gpmi.h on the resident factorisation, behind the shims' pointer checks
 int alpha_impl(gpmi_ctx* c, double* alpha_out);
@@ -340,6 +344,7 @@ void laplace_quad_nodes(double sig2, int* M, double* T, double* h);
 int softmax_fit_impl(gpmi_ctx* c, int n_classes, double sigma, double ell, double tol, int max_iter, double* log_q,
                      int* iters, int* converged, double* f_hat);
 int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t n_samples, const double* normals, double* prob);
+int softmax_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma);
 
 // sparse.hip: sparse regression with m inducing inputs (VFE / FITC) in the whitened form, and its prediction
 int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, double ell, double noise_var, double jitter,

@@ -31,6 +31,10 @@ hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out) {
     // padded tail of m is zero (identity padding), so the padded system stays consistent
     hipError_t e = hipMemcpyAsync(x2, c->m_row(), (size_t)c->Np * 8, hipMemcpyDeviceToDevice, c->stream);
     if (e != hipSuccess) return e;
+    return backward_solve_rhs(c, x2, x_out);
+}
+
+hipError_t backward_solve_rhs(gpmi_ctx* c, double* x2, double** x_out) {
     *x_out = c->res.factor_fused ? x2 + c->Np : x2;
     if (c->res.factor_fused) return backward_solve_fused(c, x2, x2 + c->Np);
     return launch_trsv_lt(c->stream, c->A.as<double>(), c->ldA, x2, c->Np);

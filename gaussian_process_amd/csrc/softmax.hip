@@ -19,6 +19,9 @@
 //   softmax_rowdot_kernel    prediction: mu* = R (Y - P)^T and B_c[i] . R[i]
 //   softmax_gram_kernel      prediction: Sigma[i] = [U_c[:, i] . U_c'[:, i]] + diag(sigma^2 - B_c[i] . R[i])
 //   softmax_sample_kernel    prediction: C x C Cholesky per test point and the mean of softmax(mu* + chol(Sigma) z_s)
+//   softmax_s2_kernel        gradient: per training point, s2 from its C x C posterior covariance and P
+//   softmax_z_kernel         gradient: z_c = s2_c - v_c + E_c t from the tile partials
+//   softmax_weight_kernel    gradient: Wm = -sum_c E_c + Gamma + sum_c (g_c g_c^T + z_c g_c^T + g_c z_c^T) on the lower tiles
 // The GEMM that forms V V^T subtracts (the fast route of gemm_nt): the buffers hold -E_c, and every consumer here takes
 // the sign back.  Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
 #include "gpmi_ctx.h"
@@ -426,6 +429,100 @@ __global__ __launch_bounds__(VEC_THREADS) void softmax_sample_kernel(int C, int6
     }
 }
 
+// Gradient, one thread per training point: P from F as softmax_newton_kernel forms it (maximum subtracted), then from the
+// point's C x C posterior covariance Sg = cov[i]
+//     q_c = Sg_cc - 2 sum_e Sg_ce pi_e,   s2_c = -(pi_c (q_c - sum_e pi_e q_e)) / 2
+// (= -1/2 sum_pq Sg_pq dW_pq/df_c for W = diag(pi) - pi pi^T; e runs in index order).  0 past N.
+__global__ __launch_bounds__(VEC_THREADS) void softmax_s2_kernel(int64_t N, int64_t Np, int C, const double* __restrict__ F,
+                                                                 const double* __restrict__ cov, double* __restrict__ s2) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    if (i >= N) {
+        for (int c = 0; c < C; ++c) s2[c * Np + i] = 0.0;
+        return;
+    }
+    double pr[MAXC], q[MAXC];
+    double fmx = -INFINITY, se = 0.0;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        pr[c] = 0.0;
+        if (c < C) { pr[c] = F[c * Np + i]; fmx = fmax(fmx, pr[c]); }
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) { pr[c] = exp(pr[c] - fmx); se += pr[c]; }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) pr[c] = pr[c] / se;
+    const double* Sg = cov + i * C * C;
+    double pq = 0.0;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        q[c] = 0.0;
+        if (c < C) {
+            double sp = 0.0;
+#pragma unroll
+            for (int e = 0; e < MAXC; ++e)
+                if (e < C) sp = fma(Sg[c * C + e], pr[e], sp);
+            q[c] = Sg[c * C + c] - 2.0 * sp;
+            pq = fma(pr[c], q[c], pq);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) s2[c * Np + i] = -0.5 * (pr[c] * (q[c] - pq));
+}
+
+// z_c = (s2_c - v_c) + E_c t from the tile partials of (-E_c) t; 0 past N
+__global__ __launch_bounds__(VEC_THREADS) void softmax_z_kernel(const double* __restrict__ part, int64_t nt, int64_t N,
+                                                                int64_t Np, int C, const double* __restrict__ s2,
+                                                                const double* __restrict__ v, double* __restrict__ z) {
+    const int64_t i = (int64_t)blockIdx.x * VEC_THREADS + threadIdx.x;
+    if (i >= Np) return;
+    const int64_t pstride = nt * nt * LT;
+    for (int c = 0; c < C; ++c) {
+        const int64_t o = c * Np + i;
+        z[o] = i < N ? (s2[o] - v[o]) - slot_sum(part + c * pstride, nt, i) : 0.0;
+    }
+}
+
+// One workgroup per lower tile (I, J) of the gradient's weight matrix, written over nGam (which holds -Gamma there):
+//     Wm = (sum_c nE_c - nGam) + sum_c (g_ci g_ck + z_ci g_ck + g_ci z_ck)
+// i.e. -sum_c E_c + Gamma plus the rank-3C term, classes in index order in both sums; one read of the C + 1 tiles and
+// one write.  The tile's row and column segments of the 2 C vectors sit in LDS (4 C x 128 doubles, dynamic).  Whole
+// tiles: the E_c are mirrored and the product behind nGam computes its diagonal tiles whole.
+__global__ __launch_bounds__(VEC_THREADS) void softmax_weight_kernel(const double* __restrict__ nE, int64_t estride, int C,
+                                                                     double* __restrict__ nGam, int64_t ld, int64_t Np,
+                                                                     const double* __restrict__ g,
+                                                                     const double* __restrict__ z) {
+    extern __shared__ __attribute__((aligned(16))) double wv[];       // [4][C][LT]: g_I, z_I, g_J, z_J
+    int64_t I, J;
+    tile_of(blockIdx.x, I, J);
+    for (int e = threadIdx.x; e < 4 * C * LT; e += VEC_THREADS) {
+        const int which = e / (C * LT), c = (e / LT) % C, t = e % LT;
+        const double* src = (which & 1) ? z : g;
+        wv[e] = src[(int64_t)c * Np + ((which & 2) ? J : I) * LT + t];
+    }
+    __syncthreads();
+    const double *gI = wv, *zI = wv + C * LT, *gJ = wv + 2 * C * LT, *zJ = wv + 3 * C * LT;
+    for (int e = threadIdx.x; e < LT * LT / 2; e += VEC_THREADS) {
+        const int r = e / (LT / 2), c0 = 2 * (e % (LT / 2));
+        const int64_t o = (I * LT + r) * ld + J * LT + c0;
+        double e0 = 0.0, e1 = 0.0, t0 = 0.0, t1 = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const d2 ev = *reinterpret_cast<const d2*>(nE + c * estride + o);
+            e0 += ev.x; e1 += ev.y;
+            const double gi = gI[c * LT + r], zi = zI[c * LT + r];
+            const d2 gk = *reinterpret_cast<const d2*>(&gJ[c * LT + c0]);
+            const d2 zk = *reinterpret_cast<const d2*>(&zJ[c * LT + c0]);
+            t0 = fma(gi, gk.x, t0); t0 = fma(zi, gk.x, t0); t0 = fma(gi, zk.x, t0);
+            t1 = fma(gi, gk.y, t1); t1 = fma(zi, gk.y, t1); t1 = fma(gi, zk.y, t1);
+        }
+        const d2 gm = *reinterpret_cast<const d2*>(nGam + o);
+        *reinterpret_cast<d2*>(nGam + o) = d2{(e0 - gm.x) + t0, (e1 - gm.y) + t1};
+    }
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
 
 // vectors per pass over a tile: the fewest passes with at most 4 vectors each, spread evenly
@@ -599,6 +696,29 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     return GPMI_OK;
 }
 
+// The latent covariance of GPML Algorithm 3.4 at np points from their cross-covariance rows R = K(points, X) (np x Np,
+// leading dimension ldr): B_c = R E_c in Bc (C np rows, leading dimension ldr), dd[i][c] = B_c[i] . R[i], one sweep
+// U_c^T = B_c M^-T over all classes, cov[i] = [U_c[i] . U_e[i]] + diag(sigma^2 - dd[i]).  The prediction runs it on
+// K(X*, X), the gradient on K itself.
+static int latent_cov(gpmi_ctx* c, const double* R, int64_t ldr, int64_t np, double* Bc, double* dd, double* cov) {
+    hipStream_t st = c->stream;
+    const int C = c->sm_classes;
+    const int64_t Np = c->Np, ld = c->ldA, msize = Np * ld;
+    const double* nE = c->sm_E.as<double>();
+    HIP_TRY(launch_fill_rows(st, Bc, ldr, C * np, Np, 0.0));
+    for (int k = 0; k < C; ++k) {                                     // B_c = R E_c = 0 - R (-E_c)^T
+        HIP_TRY(launch_gemm_nt(st, gemm_minus(Bc + (int64_t)k * np * ldr, ldr, R, ldr, nE + (int64_t)k * msize, ld, np, Np, Np)));
+    }
+    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, R, ldr, Np, (const double*)Bc,
+                       np * ldr, ldr, C, dd);                         // B_c[i] . R[i]
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(solve_sweep(c, Bc, ldr, C * np));                         // U_c^T = B_c M^-T, all classes in one sweep
+    hipLaunchKernelGGL(softmax_gram_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, (const double*)Bc, ldr, np, Np, C,
+                       c->sig2, (const double*)dd, cov);
+    HIP_TRY(hipGetLastError());
+    return GPMI_OK;
+}
+
 int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const double* normals, double* prob) {
     if (!c->res.softmax()) return fail_arg("gpmi_softmax_predict: no softmax fit resident (call gpmi_softmax_fit)");
     if (!c->res.have_test) return fail_arg("gpmi_softmax_predict: no test set (call gpmi_set_test)");
@@ -607,7 +727,8 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     TuneScope tune_scope(&tn);
     hipStream_t st = c->stream;
     const int C = c->sm_classes;
-    const int64_t Np = c->Np, np_ = c->np_, n = c->n, ld = c->ldA, msize = Np * ld;
+    const int64_t Np = c->Np, np_ = c->np_, n = c->n;
+    int rc;
     c->res.drop_v();
     c->ldV = Np + c->ld_pad;
     const int64_t ldV = c->ldV;
@@ -622,24 +743,13 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     double* o_cov = o_prob + np_ * C;
     double* o_z = o_cov + np_ * C * C;
     const double* G = c->sm.as<double>() + (int64_t)SV_G * C * Np;
-    const double* nE = c->sm_E.as<double>();
 
     const RbfArgs r = rbf_test_train(c, R, ldV);          // R = K(X*, X)
     HIP_TRY(launch_rbf(st, r));
     hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,
                        (int64_t)0, C, o_mu);                          // mu* = R (Y - P)^T
     HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_fill_rows(st, Bc, ldV, C * np_, Np, 0.0));
-    for (int k = 0; k < C; ++k) {                                     // B_c = R E_c = 0 - R (-E_c)^T
-        HIP_TRY(launch_gemm_nt(st, gemm_minus(Bc + (int64_t)k * np_ * ldV, ldV, R, ldV, nE + (int64_t)k * msize, ld, np_, Np, Np)));
-    }
-    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np,
-                       (const double*)Bc, np_ * ldV, ldV, C, o_dd);   // B_c[i] . R[i]
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(solve_sweep(c, Bc, ldV, C * np_));                        // U_c^T = B_c M^-T, all classes in one sweep
-    hipLaunchKernelGGL(softmax_gram_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)Bc, ldV, np_, Np, C,
-                       c->sig2, (const double*)o_dd, o_cov);
-    HIP_TRY(hipGetLastError());
+    if ((rc = latent_cov(c, R, ldV, np_, Bc, o_dd, o_cov)) != GPMI_OK) return rc;
     if (S > 0) {
         HIP_TRY(hipMemcpyAsync(o_z, normals, (size_t)S * C * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(softmax_sample_kernel, dim3((unsigned)n), dim3(VEC_THREADS), 0, st, C, S, (const double*)o_mu,
@@ -651,6 +761,128 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     if (S > 0) HIP_TRY(hipMemcpyAsync(prob, o_prob, (size_t)n * C * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
+    return GPMI_OK;
+}
+
+// The gradient of log q at the resident fit w.r.t. the hyper-parameters of the shared kernel (include/gpmi.h has the
+// formulas; GPML prints no algorithm for the multi-class case).  It reads M (A), K (Kn, whose lower triangle it mirrors
+// into the upper one: the same bits every call), the -E_c, F and G = Y - P, and writes scratch only:
+//   1. Sigma_i, the C x C posterior covariance at every training point: latent_cov with R = K (C matrices in sm_B)
+//   2. s2 by softmax_s2_kernel
+//   3. z = s2 - R K_blk s2: K s2_c, v_c = E_c (K s2_c), t = M^-T M^-1 sum_c v_c (the forward half as a one-row sweep in
+//      U, the backward half by the resident factor's solve), z_c = s2_c - v_c + E_c t
+//   4. -Gamma = -sum_c T_c^T T_c into the first matrix of sm_B (dead since 1.): per class U <- -E_c, the sweep
+//      U <- U M^-T = -T_c^T, and the lower-tile product by the subtracting GEMM
+//   5. Wm over -Gamma by softmax_weight_kernel
+//   6. the d + 3 sums of grad_ard_kernel in its regression form with Kn := Wm and alpha := 0 (weight = Wm_ij exactly)
+// The vectors live in loov.  V is not touched.
+int softmax_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) {
+    if (!c->res.softmax()) return fail_arg("gpmi_softmax_grad: no softmax fit resident (call gpmi_softmax_fit)");
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    hipStream_t st = c->stream;
+    const int C = c->sm_classes;
+    const int64_t N = c->N, Np = c->Np, nt = Np / TILE, ld = c->ldA, msize = Np * ld;
+    c->timers_reset({GPMI_T_GRAD});
+    // C x Np each: s2, K s2, v, z; Np each: sum_c v_c, the backward solve's two, zeros; then Sigma and the row dots
+    const size_t nvec = (size_t)(4 * C + 4 + C * C + C) * Np;
+    {
+        hipError_t e = c->sm_B.ensure((size_t)C * msize * 8);
+        if (e == hipSuccess) e = c->loov.ensure(nvec * 8);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail_runtime(e, "gpmi_softmax_grad: workspace");
+        }
+    }
+    HIP_TRY(c->sm_part.ensure((size_t)C * nt * nt * TILE * 8));
+    double* s2 = c->loov.as<double>();
+    double *ks2 = s2 + (int64_t)C * Np, *vv = ks2 + (int64_t)C * Np, *z = vv + (int64_t)C * Np;
+    double *vsum = z + (int64_t)C * Np, *x2 = vsum + Np, *zero = x2 + 2 * Np;
+    double *cov = zero + Np, *dd = cov + (int64_t)C * C * Np;
+    double* K = c->Kn.as<double>();
+    double* U = c->U.as<double>();
+    double* Bc = c->sm_B.as<double>();
+    double* part = c->sm_part.as<double>();
+    const double* nE = c->sm_E.as<double>();
+    const double* F = c->sm.as<double>() + (int64_t)SV_F * C * Np;
+    const double* G = c->sm.as<double>() + (int64_t)SV_G * C * Np;
+    const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
+    int rc;
+
+    const size_t sp = c->span_begin(GPMI_T_GRAD);
+    {                                                                 // K whole: its rows are the R of latent_cov
+        const int64_t nm = Np / MT;
+        hipLaunchKernelGGL(softmax_mirror_kernel, dim3((unsigned)(nm * (nm + 1) / 2), 1u), dim3(VEC_THREADS), 0, st, K,
+                           (int64_t)0, ld);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = latent_cov(c, K, ld, Np, Bc, dd, cov)) != GPMI_OK) return rc;                  // 1.
+    hipLaunchKernelGGL(softmax_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, C, F, (const double*)cov, s2);
+    HIP_TRY(hipGetLastError());                                                              // 2.
+
+    SymvArgs kx;                                                                             // 3.
+    kx.M = K; kx.mstride = 0; kx.ld = ld; kx.nt = nt; kx.x = s2; kx.xstride = 0; kx.nvec = C; kx.part = part;
+    HIP_TRY(launch_symv(st, kx, 1));
+    hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
+                       1.0, ks2, (double*)nullptr);
+    HIP_TRY(hipGetLastError());
+    SymvArgs ex;
+    ex.M = nE; ex.mstride = msize; ex.ld = ld; ex.nt = nt; ex.x = ks2; ex.xstride = Np; ex.nvec = 1; ex.part = part;
+    HIP_TRY(launch_symv(st, ex, C));
+    hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
+                       -1.0, vv, vsum);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_fill_rows(st, U, ld, TILE, Np, 0.0));              // M^-1 sum_c v_c: row 0 of a one-tile sweep
+    HIP_TRY(launch_set_yrow(st, U, vsum, N, Np));
+    HIP_TRY(solve_sweep(c, U, ld, TILE));
+    HIP_TRY(hipMemcpyAsync(x2, U, (size_t)Np * 8, hipMemcpyDeviceToDevice, st));
+    double* t = nullptr;
+    HIP_TRY(backward_solve_rhs(c, x2, &t));
+    ex.x = t; ex.xstride = 0;
+    HIP_TRY(launch_symv(st, ex, C));
+    hipLaunchKernelGGL(softmax_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
+                       (const double*)s2, (const double*)vv, z);
+    HIP_TRY(hipGetLastError());
+
+    HIP_TRY(launch_fill_rows(st, Bc, ld, Np, Np, 0.0));                                      // 4.
+    for (int k = 0; k < C; ++k) {
+        HIP_TRY(hipMemcpyAsync(U, nE + (int64_t)k * msize, (size_t)msize * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(solve_sweep(c, U, ld, Np));
+        HIP_TRY(neg_gram_lower_dense(c, U, Bc, ld, Np));
+    }
+    hipLaunchKernelGGL(softmax_weight_kernel, dim3(tiles), dim3(VEC_THREADS), (size_t)4 * C * LT * sizeof(double), st, nE,
+                       msize, C, Bc, ld, Np, G, (const double*)z);                           // 5.
+    HIP_TRY(hipGetLastError());
+
+    HIP_TRY(hipMemsetAsync(zero, 0, (size_t)Np * 8, st));                                    // 6.
+    GradArdArgs ga;
+    ga.Z = c->x_train(); ga.n = N; ga.d = c->d;
+    ga.alpha = zero; ga.Kn = Bc; ga.ld = ld; ga.coef = c->coef;
+    ga.family = 0;
+    const int64_t nblk = grad_ard_blocks(ga), nl = grad_ard_launches(ga), w = grad_ard_width(ga);
+    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
+    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
+    ga.partial = c->gpart.as<double>();
+    ga.sums = c->gsum.as<double>();
+    HIP_TRY(launch_grad_ard(st, ga));
+    c->span_end(sp);
+    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
+    HIP_TRY(hipMemcpyAsync(sums.data(), ga.sums, sums.size() * 8, hipMemcpyDeviceToHost, st));
+    int gave_up = 0;
+    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
+        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c->timers_collect();
+    if (gave_up) return fail_gave_up("gpmi_softmax_grad");
+    // laplace_grad_impl's scaling: sum Wm K/sigma^2 e_k^2 per dimension, then the l and sigma sums (the noise slot is unused)
+    const double l2 = c->ell * c->ell;
+    if (d_r)
+        for (int64_t k = 0; k < c->d; ++k) {
+            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
+            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
+        }
+    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
+    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
     return GPMI_OK;
 }
 

@@ -475,6 +475,15 @@ class GPContext:
                                                       ptr(prob) if S else None))
         return mu, cov, prob
 
+    def softmax_grad(self):
+        """(d_r (d,), dlog_q/dl, dlog_q/dsigma) at the resident softmax fit: the derivatives of log_q w.r.t. the relative
+        lengthscales of set_lengthscales (all 1 when none are set), the common lengthscale and sigma of the kernel the
+        classes share (gpmi_softmax_grad).  The formula holds at the mode, so fit with tol=1e-13."""
+        d_r = np.empty(self.d)
+        dl, ds = C.c_double(), C.c_double()
+        check(self._lib.gpmi_softmax_grad(self._h, ptr(d_r), C.byref(dl), C.byref(ds)))
+        return d_r, dl.value, ds.value
+
     # ---- sparse regression with inducing points (VFE / FITC) ------------------------------
     def sparse_fit(self, X, y, Z, sigma, l, noise_var, *, method="vfe", jitter=1e-6, lengthscales=KEEP):
         """Sparse GP regression with the m inducing inputs Z (m, d), m <= N (gpmi_sparse_fit): O(N m^2) work and

@@ -339,6 +339,26 @@ int gpmi_softmax_fit(gpmi_ctx* ctx, int n_classes, double sigma, double ell, dou
  *   <= 0 of the C x C Cholesky is set to 0 with its column.  n_samples 0: normals and prob NULL, no sampling. */
 int gpmi_softmax_predict_resident(gpmi_ctx* ctx, double* mu, double* cov, int64_t n_samples, const double* normals,
                                   double* prob);
+/* Gradient of log_q at the resident softmax fit w.r.t. the relative lengthscales of gpmi_set_lengthscales (d_r: d
+ * doubles, all r_k = 1 when none are set), the common lengthscale and sigma of the kernel all classes share, with the
+ * conventions of gpmi_laplace_grad; any pointer may be NULL (K has no noise term).  GPML prints no algorithm for the
+ * multi-class case (Algorithm 5.1 is binary); DESIGN.md section 4g derives this one.  With G = Y - P at the mode:
+ *   dlog_q/dtheta = 1/2 sum_ik dK_ik/dtheta Wm_ik
+ *   Wm    = -sum_c E_c + Gamma + sum_c (g_c g_c^T + z_c g_c^T + g_c z_c^T)
+ *   Gamma = sum_c E_c (M M^T)^-1 E_c = sum_c T_c^T T_c,   T_c^T = E_c M^-T
+ * (-sum_c E_c + Gamma is minus the sum of the diagonal blocks of R = (K_blk + W^-1)^-1, GPML eq. 3.47: the classes share
+ * one K, so only those blocks meet dK).  The implicit term: with Sigma_i the C x C posterior covariance of the latent
+ * values at training point i -- the cov of gpmi_softmax_predict_resident with the training set as test set -- and pi_i
+ * column i of P,
+ *   q_i = diag(Sigma_i) - 2 Sigma_i pi_i,   s2_ci = -1/2 pi_ci (q_ci - pi_i . q_i)    (= -1/2 sum_pq Sigma_i[p,q] dW_i[p,q]/df_ci)
+ *   z = s2 - R K_blk s2:   v_c = E_c (K s2_c),  t = M^-T M^-1 sum_c v_c,  z_c = s2_c - v_c + E_c t.
+ * The formula holds AT the mode: fit with tol = 1e-13, as for gpmi_laplace_grad.  About 5 C N^3 flops (per class the
+ * product K E_c, two triangular sweeps and a lower-tile product).  Only reads the fit (M, the E_c, F^, Y - P; the kept K
+ * has its lower triangle mirrored into its upper one): it stays resident and gpmi_softmax_predict_resident returns the
+ * same bits afterwards.  Device memory: C more N x N matrices; if they do not fit, GPMI_ERR_RUNTIME and the
+ * fit is still resident.  GPMI_ERR_BAD_ARG ("no softmax fit resident (call gpmi_softmax_fit)") without one.  The
+ * single-launch backward solve's give-up word is reported as by gpmi_softmax_fit.  Time: the GPMI_T_GRAD slot. */
+int gpmi_softmax_grad(gpmi_ctx* ctx, double* d_r, double* d_ell, double* d_sigma);
 
 /* Sparse GP regression with m inducing inputs Z (m x d, d as in gpmi_set_train) on the resident training set, for N far
  * beyond an N x N covariance: O(N m^2) flops, O(m^2 + N d) device memory.  GPML chapter 8; the
