@@ -1,5 +1,7 @@
 // Internal to libgpmi355x.so: the context object behind the opaque gpmi_ctx handle, the error
-// helpers every translation unit of the C-ABI shares, and the single-GPU drivers (driver.hip).
+// helpers every translation unit of the C-ABI shares (HIP_TRY, LAUNCH_TRY), the single-GPU drivers (driver.hip) and the
+// host-side pieces the fits, predictions and gradients share: regress.hip's backward solves, predict_front and ARD trace
+// ending, laplace.hip's classifier skeleton.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -33,6 +35,13 @@ inline int fail_arg(const char* what) {
     do {                                                          \
         hipError_t _e = (expr);                                   \
         if (_e != hipSuccess) return fail_runtime(_e, #expr);     \
+    } while (0)
+
+// a kernel launch that returns through fail_runtime if the launch was refused
+#define LAUNCH_TRY(kernel, grid, block, lds, stream, ...)                     \
+    do {                                                                      \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);    \
+        HIP_TRY(hipGetLastError());                                           \
     } while (0)
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
@@ -301,6 +310,17 @@ int alpha_impl(gpmi_ctx* c, double* alpha_out);
 // vec made large enough, then inside a span of that slot, which it opens: (alpha_out not null) alpha = L^-T m,
 // U = L^-T by the TRSM sweep on the identity and (want_kn) Kn = -U U^T on the lower tiles
 int factor_inverse_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span);
+// The ending of the three ARD traces (gpmi_lml_grad_ard, gpmi_laplace_grad, gpmi_softmax_grad).  grad_ard_finish, given
+// the arguments with the caller's inputs: gpart and gsum sized, the trace, the span's end, the launches' plain sums on the
+// host behind the call's one synchronisation, timers collected; solve_api not null: a backward solve ran in this call and
+// its give-up word is read and reported under that name.  grad_ard_scale: the derivatives asked for (null: skipped) from
+// the sums, d_r[k] = sig2 sum_k / (2 l2 r_k), d_ell, d_sigma and the noise slot; l2 is l^2 (a Matern family's 1 / a^2).
+int grad_ard_finish(gpmi_ctx* c, GradArdArgs& a, size_t span, const char* solve_api, std::vector<double>* sums);
+void grad_ard_scale(const gpmi_ctx* c, const GradArdArgs& a, const std::vector<double>& sums, double l2, double* d_r,
+                    double* d_ell, double* d_sigma, double* d_noise);
+// the front of the three predictions: whatever v was kept goes, V is made n_p x (Np + ld_pad) and K(X*, X) is built
+// into it, inside a span of ks_slot where that is not negative
+int predict_front(gpmi_ctx* c, int ks_slot);
 int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
 int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma);
 int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
@@ -322,16 +342,19 @@ int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_
                      int* converged, double* f_hat);
 int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* prob);
 int laplace_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma);
-// The Newton skeleton of both classifiers (laplace.hip).  classifier_fit_check: the arguments both take, under the
-// caller's API name; `own` is the text of a failed check of the caller's own arguments (or null), reported at its place
-// behind the kernel check.  classifier_fit_begin: the resident fit goes, A and the hyper-parameters are set up, the
-// backward solve's give-up word (*chain: it is read from the first iteration on) and the pivot word are reset.
-// newton_readback, behind the caller's per-point kernel: Psi from its partials with the pivot and give-up words in one
-// record, h = {Psi, pivot word, give-up word}, the iteration's one synchronisation, and the record's status under the
-// caller's API name and its text for a bad pivot.
+// The Newton skeleton of both classifiers (laplace.hip); the loop itself is newton_iterate of gpmi_state.h, which each fit
+// gives a problem object.  classifier_fit_check: the arguments both take, under the caller's API name; `own` is the text of
+// a failed check of the caller's own arguments (or null), reported at its place behind the kernel check.
+// classifier_labels_check: y on the host (one synchronisation) and `text`, behind the API name, for a label that fails ok(label, n_classes).
+// classifier_fit_begin: the resident fit goes, A and the hyper-parameters are set up, the backward solve's give-up word
+// (*chain: it is read from the first iteration on) and the pivot word are reset.  newton_readback, behind the caller's
+// per-point kernel: Psi from its partials with the pivot and give-up words in one record, h = {Psi, pivot word, give-up
+// word}, the iteration's one synchronisation, and the record's status under the caller's API name and pivot text.
 constexpr int64_t NO_BAD_PIVOT = std::numeric_limits<int64_t>::max();
 int classifier_fit_check(const gpmi_ctx* c, const char* api, const char* own, double sigma, double ell, double tol,
                          int max_iter);
+int classifier_labels_check(gpmi_ctx* c, const char* api, bool (*ok)(double label, int n_classes), int n_classes,
+                            const char* text);
 int classifier_fit_begin(gpmi_ctx* c, double sigma, double ell, bool* chain);
 hipError_t launch_newton_psi(hipStream_t st, const double* psi_part, int64_t nblk, const int64_t* info, const int* flag,
                              double* out);

@@ -1,5 +1,6 @@
-// What a context holds on the device, and the Newton step decision of the two classifiers: host-only, no HIP types (plain
-// g++ compiles it; tests/sanitize/state_check.cpp holds it to the table of tests/state_table.py on the CPU).
+// What a context holds on the device, and the Newton step decision and loop of the two classifiers: host-only, no HIP
+// types (plain g++ compiles it; tests/sanitize/state_check.cpp holds it to the table of tests/state_table.py and to the
+// classifiers' mirrors on the CPU).
 //
 // THE RULE.  A context has at most one fit resident, because every fit builds on the same buffers: a regression
 // factorisation (A holds L, the y row m = L^-1 y), a binary Laplace fit (A holds the factor of B = I + W^1/2 K W^1/2 at
@@ -81,6 +82,42 @@ inline Step newton_decide(double psi, double psi_prev, double tol, int halvings)
     if (std::fabs(d) <= thr) return Step::Converged;
     if (d < -thr && halvings < 20) return Step::Halve;
     return Step::Accept;
+}
+
+// The Newton iteration of both classifiers around newton_decide.  The problem supplies four callbacks, each returning a
+// status (non-zero ends the run at once with that status, *iters and *converged untouched):
+//   forward()             the products the objective needs from the current iterate
+//   evaluate(mode, &psi)  Psi of the fresh iterate (mode 0) or of the step halved once more (mode 1)
+//   factor(last)          the factorisations at the iterate; last: no step follows, the factor stays resident
+//   step()                the Newton step from that factor (the problem keeps the previous iterate for the halvings)
+// No line search runs before the first step; a step is halved while newton_decide says so; the run ends behind the factor
+// of a converged iterate or of iterate max_iter.  The problem keeps the last Psi it reported: it is the final iterate's.
+template <class Problem>
+int newton_iterate(Problem& p, double tol, int max_iter, int* iters, bool* converged) {
+    double psi = 0.0, psi_prev = 0.0;
+    bool have_prev = false, conv = false;
+    int it = 0, rc;
+    for (;;) {
+        if ((rc = p.forward())) return rc;
+        if ((rc = p.evaluate(0, &psi))) return rc;
+        if (have_prev) {
+            for (int halvings = 0;; ++halvings) {
+                const Step step = newton_decide(psi, psi_prev, tol, halvings);
+                if (step != Step::Halve) { conv = step == Step::Converged; break; }
+                if ((rc = p.evaluate(1, &psi))) return rc;
+            }
+        }
+        const bool last = conv || it >= max_iter;
+        if ((rc = p.factor(last))) return rc;
+        if (last) break;
+        if ((rc = p.step())) return rc;
+        psi_prev = psi;
+        have_prev = true;
+        ++it;
+    }
+    *iters = it;
+    *converged = conv;
+    return 0;
 }
 
 }  // namespace gpmi

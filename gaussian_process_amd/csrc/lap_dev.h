@@ -1,6 +1,6 @@
 // Device helpers shared by the two Laplace classifiers (laplace.hip: binary, softmax.hip: multi-class): the enumeration
 // of the lower 128 x 128 tiles, the fixed-order sum of the tile partials of a matrix-vector product, and the fixed-order
-// workgroup reduction.
+// workgroup reduction; and the grid of their one-thread-per-element kernels.
 #pragma once
 #include "gpmi_ctx.h"
 
@@ -12,6 +12,9 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int LT = 128;        // tile edge (TILE)
 constexpr int SYMV_THREADS = 256;
 constexpr int VEC_THREADS = 256;
+
+// workgroups of VEC_THREADS threads that cover n elements
+inline unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
 
 // lower tile t (row-major enumeration of the lower triangle) -> (I, J), J <= I
 __device__ __forceinline__ void tile_of(int64_t t, int64_t& I, int64_t& J) {

@@ -16,6 +16,9 @@
 //   laplace_s2_kernel           gradient: s2 = -(1 - [B^-1]_ii) (1 - 2 pi) / 2 from kappa and f^
 //   laplace_z_kernel            gradient: z = s2 + s o (Kn t) from the tile partials
 // Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
+// Host side: the fit is a problem object (LaplaceNewton) for newton_iterate of gpmi_state.h, which owns the loop; what
+// softmax.hip shares is classifier_fit_check, classifier_labels_check, classifier_fit_begin and newton_readback; the
+// gradient ends in regress.hip's ARD trace ending (grad_ard_finish, grad_ard_scale), the prediction starts with predict_front.
 #include "gpmi_ctx.h"
 #include "lap_dev.h"
 
@@ -282,8 +285,6 @@ __global__ __launch_bounds__(VEC_THREADS) void laplace_z_kernel(const double* __
     z[i] = i < N ? fma(s[i], slot_sum(part, nt, i), s2[i]) : 0.0;
 }
 
-unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
-
 }  // namespace
 
 hipError_t launch_newton_psi(hipStream_t st, const double* psi_part, int64_t nblk, const int64_t* info, const int* flag,
@@ -316,6 +317,15 @@ int classifier_fit_check(const gpmi_ctx* c, const char* api, const char* own, do
         return fail_arg((who + "ell must be non-zero and hyper-parameters finite").c_str());
     if (!(tol >= 0.0) || !std::isfinite(tol)) return fail_arg((who + "tol must be finite and >= 0").c_str());
     if (max_iter < 0) return fail_arg((who + "max_iter must be >= 0").c_str());
+    return GPMI_OK;
+}
+
+int classifier_labels_check(gpmi_ctx* c, const char* api, bool (*ok)(double, int), int n_classes, const char* text) {
+    std::vector<double> hy((size_t)c->N);
+    HIP_TRY(hipMemcpyAsync(hy.data(), c->y.p, (size_t)c->N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (double v : hy)
+        if (!ok(v, n_classes)) return fail_arg((std::string(api) + ": " + text).c_str());
     return GPMI_OK;
 }
 
@@ -381,84 +391,88 @@ static hipError_t launch_symv(gpmi_ctx* c, double* M, int64_t ld, bool scale, co
 
 static const char* const PIVOT_TEXT = "B = I + W^1/2 K W^1/2 met a non-positive pivot";
 
+// The binary fit as newton_iterate's problem (gpmi_state.h).  h is the last read-back record: h[0] ends as Psi(f^).
+namespace {
+struct LaplaceNewton {
+    gpmi_ctx* c;
+    bool chain;
+    int64_t nblk;
+    NewtonVecs v;
+    RbfArgs r;                 // K into A
+    double *psi_part, *rec;
+    double h[3];
+
+    int forward() {
+        HIP_TRY(launch_rbf(c->stream, r));                            // 1. K
+        HIP_TRY(launch_symv(c, c->A.as<double>(), c->ldA, false, v.a));   // 2. f = K a
+        return GPMI_OK;
+    }
+    // 3., 4. Psi of the iterate, with the previous Cholesky's pivot word and backward solve's give-up word
+    int evaluate(int mode, double* psi) {
+        LAUNCH_TRY(laplace_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, c->stream, mode,
+                   (const double*)c->lap_part.as<double>(), c->Np / TILE, c->N, c->Np, (const double*)c->y.as<double>(), v,
+                   psi_part);
+        const int rc = newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_laplace_fit", PIVOT_TEXT);
+        *psi = h[0];
+        return rc;
+    }
+    int factor(bool) {
+        hipStream_t st = c->stream;
+        const int64_t N = c->N, Np = c->Np;
+        double* cv = c->lap.as<double>() + LV_C * Np;
+        HIP_TRY(launch_symv(c, c->A.as<double>(), c->ldA, true, v.b));    // 5. u = K b, K <- B
+        LAUNCH_TRY(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)c->lap_part.as<double>(),
+                   Np / TILE, N, Np, (const double*)v.s, cv);
+        HIP_TRY(launch_set_yrow(st, c->m_row(), cv, N, Np));          // 6. c rides: m = L^-1 c
+        HIP_TRY(cholesky_inplace(c, c->A.as<double>(), c->ldA, Np, c->Mp, c->info.as<int64_t>(), false));
+        c->res.factor_replaced(tuning().panel_fused);
+        return GPMI_OK;
+    }
+    int step() {
+        double* x = nullptr;                                          // 7. x = L^-T m, a = b - s o x
+        HIP_TRY(backward_solve_resident(c, c->lap.as<double>() + LV_X * c->Np, &x));
+        LAUNCH_TRY(laplace_update_kernel, dim3(grid_of(c->Np)), dim3(VEC_THREADS), 0, c->stream, c->N, c->Np,
+                   (const double*)x, v);
+        return GPMI_OK;
+    }
+};
+}  // namespace
+
 int laplace_fit_impl(gpmi_ctx* c, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat) {
     int rc = classifier_fit_check(c, "gpmi_laplace_fit", nullptr, sigma, ell, tol, max_iter);
     if (rc) return rc;
-    hipStream_t st = c->stream;
-    const int64_t N = c->N;
-    {
-        std::vector<double> hy((size_t)N);
-        HIP_TRY(hipMemcpyAsync(hy.data(), c->y.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (double v : hy)
-            if (v != 1.0 && v != -1.0) return fail_arg("gpmi_laplace_fit: labels must be exactly -1 or +1");
-    }
+    if ((rc = classifier_labels_check(c, "gpmi_laplace_fit", [](double v, int) { return v == 1.0 || v == -1.0; }, 2,
+                                      "labels must be exactly -1 or +1")))
+        return rc;
     bool chain = false;
     if ((rc = classifier_fit_begin(c, sigma, ell, &chain)) != GPMI_OK) return rc;
-    const int64_t Np = c->Np, nt = Np / TILE;
+    hipStream_t st = c->stream;
+    const int64_t N = c->N, Np = c->Np, nt = Np / TILE;
     const int64_t nblk = (Np + VEC_THREADS - 1) / VEC_THREADS;
     HIP_TRY(c->lap.ensure(((size_t)LV_COUNT * Np + 2 * nblk + 8) * 8));
     HIP_TRY(c->lap_part.ensure((size_t)nt * nt * TILE * 8));
-    double* L = c->lap.as<double>();
-    double* psi_part = L + LV_COUNT * Np;
-    double* rec = psi_part + 2 * nblk;
-    const NewtonVecs v = newton_vecs(c);
     double* A = c->A.as<double>();
-    HIP_TRY(hipMemsetAsync(v.a, 0, (size_t)Np * 8, st));
+    LaplaceNewton p;
+    p.c = c; p.chain = chain; p.nblk = nblk; p.v = newton_vecs(c);
+    p.psi_part = c->lap.as<double>() + LV_COUNT * Np; p.rec = p.psi_part + 2 * nblk;
+    p.r = rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, A, c->ldA);
+    HIP_TRY(hipMemsetAsync(p.v.a, 0, (size_t)Np * 8, st));
     HIP_TRY(launch_fill_rows(st, c->m_row(), c->ldA, TILE, Np, 0.0));
-    const RbfArgs r = rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, A, c->ldA);
-
-    // Psi of the current iterate, with the previous Cholesky's pivot word and backward solve's give-up word
-    double h[3];
-    auto evaluate = [&](int mode) -> int {
-        hipLaunchKernelGGL(laplace_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, st, mode,
-                           (const double*)c->lap_part.as<double>(), nt, N, Np, (const double*)c->y.as<double>(), v, psi_part);
-        HIP_TRY(hipGetLastError());
-        return newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_laplace_fit", PIVOT_TEXT);
-    };
-
-    double psi_prev = 0.0;
-    bool have_prev = false, conv = false;
     int it = 0;
-    for (;;) {
-        HIP_TRY(launch_rbf(st, r));                                   // 1. K
-        HIP_TRY(launch_symv(c, A, c->ldA, false, v.a));                          // 2. f = K a
-        if ((rc = evaluate(0)) != GPMI_OK) return rc;                 // 3.
-        if (have_prev) {                                              // 4.
-            for (int halvings = 0;; ++halvings) {
-                const Step step = newton_decide(h[0], psi_prev, tol, halvings);
-                if (step != Step::Halve) { conv = step == Step::Converged; break; }
-                if ((rc = evaluate(1)) != GPMI_OK) return rc;
-            }
-        }
-        HIP_TRY(launch_symv(c, A, c->ldA, true, v.b));                           // 5. u = K b, K <- B
-        hipLaunchKernelGGL(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
-                           (const double*)c->lap_part.as<double>(), nt, N, Np, (const double*)v.s, L + LV_C * Np);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(launch_set_yrow(st, c->m_row(), L + LV_C * Np, N, Np));   // 6. c rides: m = L^-1 c
-        HIP_TRY(cholesky_inplace(c, A, c->ldA, Np, c->Mp, c->info.as<int64_t>(), false));
-        c->res.factor_replaced(tuning().panel_fused);
-        if (conv || it >= max_iter) break;
-        double* x = nullptr;                                          // 7. x = L^-T m, a = b - s o x
-        HIP_TRY(backward_solve_resident(c, L + LV_X * Np, &x));
-        hipLaunchKernelGGL(laplace_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, (const double*)x, v);
-        HIP_TRY(hipGetLastError());
-        psi_prev = h[0];
-        have_prev = true;
-        ++it;
-    }
+    bool conv = false;
+    if ((rc = newton_iterate(p, tol, max_iter, &it, &conv)) != GPMI_OK) return rc;
     // log q = Psi(f^) - sum log L_ii(B(f^))  (GPML eq. 3.32 at the mode)
-    HIP_TRY(launch_lml_reduce(st, A, c->ldA, c->m_row(), N, rec + 4));
+    HIP_TRY(launch_lml_reduce(st, A, c->ldA, c->m_row(), N, p.rec + 4));
     double red[2];
     int64_t info = 0;
-    HIP_TRY(hipMemcpyAsync(red, rec + 4, sizeof red, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(red, p.rec + 4, sizeof red, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, st));
-    if (f_hat) HIP_TRY(hipMemcpyAsync(f_hat, v.f, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+    if (f_hat) HIP_TRY(hipMemcpyAsync(f_hat, p.v.f, (size_t)N * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
     if (info != NO_BAD_PIVOT) { g_err = std::string("gpmi_laplace_fit: ") + PIVOT_TEXT; return GPMI_ERR_NOT_PD; }
-    if (log_q) *log_q = h[0] - red[0];
+    if (log_q) *log_q = p.h[0] - red[0];
     if (iters) *iters = it;
     if (converged) *converged = conv ? 1 : 0;
     c->res.fit_done(Fit::Laplace);
@@ -472,27 +486,21 @@ int laplace_predict_impl(gpmi_ctx* c, double* f_mean, double* f_var, double* pro
     TuneScope tune_scope(&tn);
     hipStream_t st = c->stream;
     const int64_t Np = c->Np, np_ = c->np_, n = c->n;
-    c->res.drop_v();
-    c->ldV = Np + c->ld_pad;
-    HIP_TRY(c->V.ensure((size_t)np_ * c->ldV * 8));
     HIP_TRY(c->lap_out.ensure((size_t)np_ * 5 * 8));
+    int rc = predict_front(c, -1);                        // R = K(X*, X)
+    if (rc) return rc;
     double* V = c->V.as<double>();
     double* o = c->lap_out.as<double>();
     const double* grad = c->lap.as<double>() + LV_G * Np;
     const double* s = c->lap.as<double>() + LV_S * Np;
-
-    const RbfArgs r = rbf_test_train(c, V, c->ldV);       // R = K(X*, X)
-    HIP_TRY(launch_rbf(st, r));
-    hipLaunchKernelGGL(laplace_rows_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, V, c->ldV, Np, grad, s, o);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(laplace_rows_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, V, c->ldV, Np, grad, s, o);
     HIP_TRY(solve_sweep(c, V, c->ldV, np_));                        // v^T = (R W^1/2) L^-T
     HIP_TRY(launch_row_dots(st, V, c->ldV, np_, Np, grad, o + np_, o + 2 * np_));
     int M = 0;
     double T = 0., hq = 0.;
     laplace_quad_nodes(c->sig2, &M, &T, &hq);
-    hipLaunchKernelGGL(laplace_quad_kernel, dim3(grid_of(n)), dim3(VEC_THREADS), 0, st, n, (const double*)o,
-                       (const double*)(o + 2 * np_), c->sig2, M, T, hq, o + 3 * np_, o + 4 * np_);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(laplace_quad_kernel, dim3(grid_of(n)), dim3(VEC_THREADS), 0, st, n, (const double*)o,
+               (const double*)(o + 2 * np_), c->sig2, M, T, hq, o + 3 * np_, o + 4 * np_);
     if (f_mean) HIP_TRY(hipMemcpyAsync(f_mean, o, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     if (f_var) HIP_TRY(hipMemcpyAsync(f_var, o + 3 * np_, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     if (prob) HIP_TRY(hipMemcpyAsync(prob, o + 4 * np_, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -522,43 +530,23 @@ int laplace_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) 
     const double* L = c->lap.as<double>();
     const double *a = L + LV_A * Np, *f = L + LV_F * Np, *s = L + LV_S * Np, *g = L + LV_G * Np;
     HIP_TRY(launch_loo_kappa(st, Kb, ld, N, kappa));                 // U is still L^-T here
-    hipLaunchKernelGGL(laplace_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, (const double*)kappa, f, s2);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(laplace_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, (const double*)kappa, f, s2);
     HIP_TRY(launch_rbf(st, rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, Kb, ld)));
     HIP_TRY(launch_symv(c, Kb, ld, false, s2));
-    hipLaunchKernelGGL(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
-                       (const double*)c->lap_part.as<double>(), nt, N, Np, s, t);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(laplace_rhs_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)c->lap_part.as<double>(), nt,
+               N, Np, s, t);
     HIP_TRY(launch_symv(c, Kn, ld, false, t));
-    hipLaunchKernelGGL(laplace_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st,
-                       (const double*)c->lap_part.as<double>(), nt, N, Np, s, (const double*)s2, z);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(laplace_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)c->lap_part.as<double>(), nt,
+               N, Np, s, (const double*)s2, z);
 
     GradArdArgs ga;
     ga.Z = c->x_train(); ga.n = N; ga.d = c->d;
     ga.alpha = a; ga.Kn = Kn; ga.ld = ld; ga.coef = c->coef;
     ga.family = 0;
     ga.lap_s = s; ga.lap_z = z; ga.lap_g = g;
-    const int64_t nblk = grad_ard_blocks(ga), nl = grad_ard_launches(ga), w = grad_ard_width(ga);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
-    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
-    ga.partial = c->gpart.as<double>();
-    ga.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_ard(st, ga));
-    c->span_end(sp);
-    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
-    HIP_TRY(hipMemcpyAsync(sums.data(), ga.sums, sums.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    c->timers_collect();
-    // the plain sums of lml_grad_ard_impl, with its factors: sum w K/sigma^2 e_k^2 per dimension, then the l and sigma sums
-    const double l2 = c->ell * c->ell;
-    if (d_r)
-        for (int64_t k = 0; k < c->d; ++k) {
-            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
-            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
-        }
-    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
-    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
+    std::vector<double> sums;                             // no backward solve ran: no give-up word to read
+    if ((rc = grad_ard_finish(c, ga, sp, nullptr, &sums))) return rc;
+    grad_ard_scale(c, ga, sums, c->ell * c->ell, d_r, d_ell, d_sigma, nullptr);
     return GPMI_OK;
 }
 

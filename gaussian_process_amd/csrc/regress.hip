@@ -57,6 +57,37 @@ static int solve_epilogue(gpmi_ctx* c, const char* api) {
     return gave_up ? fail_gave_up(api) : GPMI_OK;
 }
 
+int grad_ard_finish(gpmi_ctx* c, GradArdArgs& a, size_t span, const char* solve_api, std::vector<double>* sums) {
+    hipStream_t s = c->stream;
+    const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
+    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
+    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
+    a.partial = c->gpart.as<double>();
+    a.sums = c->gsum.as<double>();
+    HIP_TRY(launch_grad_ard(s, a));
+    c->span_end(span);
+    sums->resize((size_t)nl * (size_t)(w + 3));
+    HIP_TRY(hipMemcpyAsync(sums->data(), a.sums, sums->size() * 8, hipMemcpyDeviceToHost, s));
+    if (solve_api) return solve_epilogue(c, solve_api);
+    HIP_TRY(hipStreamSynchronize(s));
+    c->timers_collect();
+    return GPMI_OK;
+}
+
+// launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums
+void grad_ard_scale(const gpmi_ctx* c, const GradArdArgs& a, const std::vector<double>& sums, double l2, double* d_r,
+                    double* d_ell, double* d_sigma, double* d_noise) {
+    const int64_t w = grad_ard_width(a);
+    if (d_r)
+        for (int64_t k = 0; k < c->d; ++k) {
+            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
+            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
+        }
+    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
+    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
+    if (d_noise) *d_noise = .5 * sums[(size_t)w + 2];
+}
+
 int alpha_impl(gpmi_ctx* c, double* alpha_out) {
     if (!c->res.regression()) return fail_arg("gpmi_get_alpha: no factorisation resident");
     c->timers_reset({GPMI_T_ALPHA});
@@ -69,23 +100,27 @@ int alpha_impl(gpmi_ctx* c, double* alpha_out) {
     return solve_epilogue(c, "gpmi_get_alpha");
 }
 
+int predict_front(gpmi_ctx* c, int ks_slot) {
+    c->res.drop_v();
+    c->ldV = c->Np + c->ld_pad;
+    HIP_TRY(c->V.ensure((size_t)c->np_ * c->ldV * 8));
+    const size_t sp = ks_slot >= 0 ? c->span_begin(ks_slot) : gpmi_ctx::NO_SPAN;
+    HIP_TRY(launch_rbf(c->stream, rbf_test_train(c, c->V.as<double>(), c->ldV)));
+    c->span_end(sp);
+    return GPMI_OK;
+}
+
 int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd) {
     if (!c->res.regression()) return fail_arg("gpmi_predict: no factorisation resident (call gpmi_factorize)");
     if (!c->res.have_test) return fail_arg("gpmi_predict: no test set (call gpmi_set_test)");
     hipStream_t s = c->stream;
     c->timers_reset({GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR});
-    c->res.drop_v();
-    c->ldV = c->Np + c->ld_pad;
-    HIP_TRY(c->V.ensure((size_t)c->np_ * c->ldV * 8));
     HIP_TRY(c->vec.ensure((size_t)std::max(c->Np, c->np_) * 4 * 8));
+    int rc = predict_front(c, GPMI_T_KS);
+    if (rc) return rc;
     double* V = c->V.as<double>();
 
-    size_t sp = c->span_begin(GPMI_T_KS);
-    const RbfArgs r = rbf_test_train(c, V, c->ldV);
-    HIP_TRY(launch_rbf(s, r));
-    c->span_end(sp);
-
-    sp = c->span_begin(GPMI_T_SOLVE_V);
+    size_t sp = c->span_begin(GPMI_T_SOLVE_V);
     HIP_TRY(solve_sweep(c, V, c->ldV, c->np_));
     c->span_end(sp);
 
@@ -176,32 +211,15 @@ int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     int rc = grad_front(c, "gpmi_lml_grad_ard: no factorisation resident (call gpmi_factorize)",
                         "gpmi_lml_grad_ard: squared-exponential or Matern kernel only (kinds 0, 4, 5, 6)", GPMI_T_GRAD, true, &alpha, &sp);
     if (rc) return rc;
-    hipStream_t s = c->stream;
     GradArdArgs a;
     a.Z = c->x_train(); a.n = c->N; a.d = c->d;
     a.alpha = alpha; a.Kn = c->Kn.as<double>(); a.ld = c->ldA; a.coef = c->coef;
     a.family = cov_family(c->kind);
-    const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
-    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
-    a.partial = c->gpart.as<double>();
-    a.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_ard(s, a));
-    c->span_end(sp);
-    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
-    HIP_TRY(hipMemcpyAsync(sums.data(), a.sums, sums.size() * 8, hipMemcpyDeviceToHost, s));
-    if ((rc = solve_epilogue(c, "gpmi_lml_grad_ard"))) return rc;
-    // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums; a Matern
-    // kind has H(t) for K/sigma^2 in the lengthscale sums and a^2 for 1 / l^2
+    std::vector<double> sums;
+    if ((rc = grad_ard_finish(c, a, sp, "gpmi_lml_grad_ard", &sums))) return rc;
+    // a Matern kind has H(t) for K/sigma^2 in the lengthscale sums and a^2 for 1 / l^2
     const double l2 = a.family ? 1.0 / cov_inv_l2(c->kind, c->ell, c->coef) : c->ell * c->ell;
-    if (d_r)
-        for (int64_t k = 0; k < c->d; ++k) {
-            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
-            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
-        }
-    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
-    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
-    if (d_noise) *d_noise = .5 * sums[(size_t)w + 2];
+    grad_ard_scale(c, a, sums, l2, d_r, d_ell, d_sigma, d_noise);
     return GPMI_OK;
 }
 

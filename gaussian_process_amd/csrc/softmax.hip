@@ -15,7 +15,8 @@
 //   softmax_vec_kernel       C vectors from the tile partials (K b_c; c_c = E_c K b_c and sum_c c_c)
 //   softmax_esum_kernel      A <- sum_c E_c on the lower tiles (identity on the padding)
 //   softmax_update_kernel    A <- B - C + [E_c t]_c (keeping the previous A, F for step halving)
-//   softmax_mirror_kernel    lower triangle of every E_c -> its upper triangle (prediction multiplies by the full matrix)
+//   (launch_mirror_lower of grad.hip: lower triangle of every E_c -> its upper triangle, prediction multiplies by the
+//   full matrix; the gradient mirrors K the same way)
 //   softmax_rowdot_kernel    prediction: mu* = R (Y - P)^T and B_c[i] . R[i]
 //   softmax_gram_kernel      prediction: Sigma[i] = [U_c[:, i] . U_c'[:, i]] + diag(sigma^2 - B_c[i] . R[i])
 //   softmax_sample_kernel    prediction: C x C Cholesky per test point and the mean of softmax(mu* + chol(Sigma) z_s)
@@ -24,6 +25,8 @@
 //   softmax_weight_kernel    gradient: Wm = -sum_c E_c + Gamma + sum_c (g_c g_c^T + z_c g_c^T + g_c z_c^T) on the lower tiles
 // The GEMM that forms V V^T subtracts (the fast route of gemm_nt): the buffers hold -E_c, and every consumer here takes
 // the sign back.  Every reduction runs in a fixed order (no atomics), so two fits give the same bits.
+// Host side: the fit is a problem object (SoftmaxNewton) for newton_iterate of gpmi_state.h, with the skeleton of
+// laplace.hip; the gradient ends in regress.hip's ARD trace ending, which reads the backward solve's give-up word here.
 #include "gpmi_ctx.h"
 #include "lap_dev.h"
 
@@ -34,7 +37,6 @@ namespace {
 using namespace lapdev;
 
 constexpr int MAXC = GPMI_SOFTMAX_MAX_CLASSES;
-constexpr int MT = 32;         // sub-tile edge of the mirror kernel
 
 struct SymvArgs {
     const double* M;           // matrix m at M + m * mstride, leading dimension ld, nt x nt tiles (lower ones are read)
@@ -193,20 +195,6 @@ __global__ __launch_bounds__(VEC_THREADS) void softmax_esum_kernel(const double*
         if (gi == gj + 1 && gi >= N) a1 = 1.0;
         *reinterpret_cast<d2*>(out + gi * ld + gj) = d2{a0, a1};
     }
-}
-
-// blockIdx.x: lower 32 x 32 sub-tile (bi, bj) of matrix blockIdx.y; (bj, bi) <- its transpose (the diagonal sub-tile's
-// upper triangle from its lower one)
-__global__ __launch_bounds__(VEC_THREADS) void softmax_mirror_kernel(double* __restrict__ E, int64_t estride, int64_t ld) {
-    __shared__ double t[MT][MT + 1];
-    int64_t bi, bj;
-    tile_of(blockIdx.x, bi, bj);
-    double* M = E + (int64_t)blockIdx.y * estride;
-    const int tx = threadIdx.x % MT, ty = threadIdx.x / MT;          // 32 x 8
-    for (int r = ty; r < MT; r += VEC_THREADS / MT) t[r][tx] = M[(bi * MT + r) * ld + bj * MT + tx];
-    __syncthreads();
-    for (int r = ty; r < MT; r += VEC_THREADS / MT)
-        if (bi != bj || tx > r) M[(bj * MT + r) * ld + bi * MT + tx] = t[tx][r];
 }
 
 struct SoftVecs {          // each C x Np, class-major
@@ -523,8 +511,6 @@ __global__ __launch_bounds__(VEC_THREADS) void softmax_weight_kernel(const doubl
     }
 }
 
-unsigned grid_of(int64_t n) { return (unsigned)((n + VEC_THREADS - 1) / VEC_THREADS); }
-
 // vectors per pass over a tile: the fewest passes with at most 4 vectors each, spread evenly
 int symv_chunk(int nvec) {
     const int passes = (nvec + 3) / 4;
@@ -552,25 +538,97 @@ enum { SW_CSUM, SW_X, SW_VECS = SW_X + 2 };
 
 static const char* const PIVOT_TEXT = "a Cholesky factorisation met a non-positive pivot";
 
+// The multi-class fit as newton_iterate's problem (gpmi_state.h).  h is the last read-back record: h[0] ends as Psi at
+// the mode.
+namespace {
+struct SoftmaxNewton {
+    gpmi_ctx* c;
+    int C;
+    bool chain;
+    int64_t nblk;
+    SoftVecs v;
+    double *K, *V, *nE, *part;     // Kn, U, sm_E, sm_part
+    double *kb, *cc, *wv;          // K B and C (C x Np each), the Np-vectors behind the matrices of c->sm
+    double *psi_part, *rec, *zrec; // ... then the Psi partials, the read-back record, the log-diagonal sums
+    SymvArgs kx, ex;               // K times C vectors; -E_c times one vector each
+    double h[3];
+
+    int forward() {
+        kx.x = v.a;                                                   // 1. F = A K
+        HIP_TRY(launch_symv(c->stream, kx, 1));
+        return GPMI_OK;
+    }
+    // 1., 2. Psi of the iterate, with the previous Cholesky's pivot word and backward solve's give-up word
+    int evaluate(int mode, double* psi) {
+        LAUNCH_TRY(softmax_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, c->stream, mode, (const double*)part,
+                   c->Np / TILE, c->N, c->Np, C, (const double*)c->y.as<double>(), v, psi_part);
+        const int rc = newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_softmax_fit", PIVOT_TEXT);
+        *psi = h[0];
+        return rc;
+    }
+    int factor(bool last) {
+        hipStream_t st = c->stream;
+        const int64_t N = c->N, Np = c->Np, nt = Np / TILE, ld = c->ldA, msize = Np * ld;
+        const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
+        double* A = c->A.as<double>();
+        // 3. per class: L_c = chol(I + s_c s_c^T o K) in A, V = S_c L_c^-T, -E_c = -V V^T (lower tiles)
+        HIP_TRY(launch_fill_rows(st, c->m_row(), ld, TILE, Np, 0.0));     // nothing rides in these factorisations
+        for (int k = 0; k < C; ++k) {
+            const double* sk = v.s + (int64_t)k * Np;
+            LAUNCH_TRY(softmax_bmat_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)K, A, ld, N, sk);
+            HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
+            c->res.factor_replaced(tuning().panel_fused);
+            HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * k));
+            HIP_TRY(launch_fill_rows(st, V, ld, Np, Np, 0.0));
+            LAUNCH_TRY(softmax_seed_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, V, ld, Np, sk);
+            HIP_TRY(solve_sweep(c, V, ld, Np, true));
+            HIP_TRY(neg_gram_lower(c, V, nE + (int64_t)k * msize, ld, Np));
+        }
+        if (!last) {                                                  // 4. c_c = E_c (K b_c), sum_c c_c rides with M
+            kx.x = v.b;
+            HIP_TRY(launch_symv(st, kx, 1));
+            LAUNCH_TRY(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C, 1.0,
+                       kb, (double*)nullptr);
+            ex.x = kb; ex.xstride = Np;
+            HIP_TRY(launch_symv(st, ex, C));
+            LAUNCH_TRY(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C, -1.0,
+                       cc, wv + SW_CSUM * Np);
+            HIP_TRY(launch_set_yrow(st, c->m_row(), wv + SW_CSUM * Np, N, Np));
+        }
+        // 5. M = chol(sum_c E_c) in A
+        LAUNCH_TRY(softmax_esum_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)nE, msize, C, A, ld, N);
+        HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
+        c->res.factor_replaced(tuning().panel_fused);
+        HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * C));
+        return GPMI_OK;
+    }
+    int step() {
+        const int64_t Np = c->Np;
+        double* x = nullptr;                                          // 6. t = M^-T M^-1 sum_c c_c, A <- B - C + [E_c t]
+        HIP_TRY(backward_solve_resident(c, wv + SW_X * Np, &x));
+        ex.x = x; ex.xstride = 0;
+        HIP_TRY(launch_symv(c->stream, ex, C));
+        LAUNCH_TRY(softmax_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, c->stream, (const double*)part, Np / TILE,
+                   c->N, Np, C, (const double*)cc, v);
+        return GPMI_OK;
+    }
+};
+}  // namespace
+
 int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, int max_iter, double* log_q, int* iters,
                      int* converged, double* f_hat) {
     int rc = classifier_fit_check(c, "gpmi_softmax_fit",
                                   C < 2 || C > MAXC ? "n_classes must lie in [2, GPMI_SOFTMAX_MAX_CLASSES]" : nullptr, sigma,
                                   ell, tol, max_iter);
     if (rc) return rc;
-    hipStream_t st = c->stream;
-    const int64_t N = c->N;
-    {
-        std::vector<double> hy((size_t)N);
-        HIP_TRY(hipMemcpyAsync(hy.data(), c->y.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (double v : hy)
-            if (!(v >= 0.0 && v < (double)C && v == std::floor(v)))
-                return fail_arg("gpmi_softmax_fit: labels must be integers in [0, n_classes)");
-    }
+    if ((rc = classifier_labels_check(c, "gpmi_softmax_fit",
+                                      [](double v, int nc) { return v >= 0.0 && v < (double)nc && v == std::floor(v); },
+                                      C, "labels must be integers in [0, n_classes)")))
+        return rc;
     bool chain = false;
     if ((rc = classifier_fit_begin(c, sigma, ell, &chain)) != GPMI_OK) return rc;
-    const int64_t Np = c->Np, nt = Np / TILE, ld = c->ldA;
+    hipStream_t st = c->stream;
+    const int64_t N = c->N, Np = c->Np, nt = Np / TILE, ld = c->ldA;
     const int64_t nblk = (Np + VEC_THREADS - 1) / VEC_THREADS;
     const int64_t msize = Np * ld;                  // doubles of one N x N matrix
     HIP_TRY(c->Kn.ensure((size_t)msize * 8));       // K
@@ -580,115 +638,34 @@ int softmax_fit_impl(gpmi_ctx* c, int C, double sigma, double ell, double tol, i
     HIP_TRY(c->sm_part.ensure((size_t)C * nt * nt * TILE * 8));
     double* Sm = c->sm.as<double>();
     auto mat = [&](int k) { return Sm + (int64_t)k * C * Np; };
-    double* wv = Sm + (int64_t)SV_MATS * C * Np;
-    double* psi_part = wv + SW_VECS * Np;
-    double* rec = psi_part + 2 * nblk;
-    double* zrec = rec + 8;
-    const SoftVecs v{mat(SV_A), mat(SV_AP), mat(SV_F), mat(SV_FP), mat(SV_S), mat(SV_G), mat(SV_B)};
-    double* A = c->A.as<double>();
-    double* K = c->Kn.as<double>();
-    double* V = c->U.as<double>();
-    double* nE = c->sm_E.as<double>();
-    double* part = c->sm_part.as<double>();
-    const unsigned tiles = (unsigned)(nt * (nt + 1) / 2);
-    HIP_TRY(hipMemsetAsync(v.a, 0, (size_t)C * Np * 8, st));
-    const RbfArgs r = rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, K, ld);    // K, once per fit
-    HIP_TRY(launch_rbf(st, r));
-
-    SymvArgs kx;                          // K times C vectors
-    kx.M = K; kx.mstride = 0; kx.ld = ld; kx.nt = nt; kx.xstride = 0; kx.nvec = C; kx.part = part;
-    SymvArgs ex;                          // -E_c times one vector each
-    ex.M = nE; ex.mstride = msize; ex.ld = ld; ex.nt = nt; ex.nvec = 1; ex.part = part;
-
-    double h[3];
-    auto evaluate = [&](int mode) -> int {
-        hipLaunchKernelGGL(softmax_newton_kernel, dim3((unsigned)nblk), dim3(VEC_THREADS), 0, st, mode, (const double*)part,
-                           nt, N, Np, C, (const double*)c->y.as<double>(), v, psi_part);
-        HIP_TRY(hipGetLastError());
-        return newton_readback(c, psi_part, nblk, chain, rec, h, "gpmi_softmax_fit", PIVOT_TEXT);
-    };
-
-    double psi_prev = 0.0;
-    bool have_prev = false, conv = false;
+    SoftmaxNewton p;
+    p.c = c; p.C = C; p.chain = chain; p.nblk = nblk;
+    p.v = SoftVecs{mat(SV_A), mat(SV_AP), mat(SV_F), mat(SV_FP), mat(SV_S), mat(SV_G), mat(SV_B)};
+    p.K = c->Kn.as<double>(); p.V = c->U.as<double>(); p.nE = c->sm_E.as<double>(); p.part = c->sm_part.as<double>();
+    p.kb = mat(SV_KB); p.cc = mat(SV_CC); p.wv = mat(SV_MATS);
+    p.psi_part = p.wv + SW_VECS * Np; p.rec = p.psi_part + 2 * nblk; p.zrec = p.rec + 8;
+    p.kx.M = p.K; p.kx.mstride = 0; p.kx.ld = ld; p.kx.nt = nt; p.kx.xstride = 0; p.kx.nvec = C; p.kx.part = p.part;
+    p.ex.M = p.nE; p.ex.mstride = msize; p.ex.ld = ld; p.ex.nt = nt; p.ex.nvec = 1; p.ex.part = p.part;
+    HIP_TRY(hipMemsetAsync(p.v.a, 0, (size_t)C * Np * 8, st));
+    HIP_TRY(launch_rbf(st, rbf_sym(c, c->x_train(), N, c->box_train(), 0.0, Np, p.K, ld)));    // K, once per fit
     int it = 0;
-    for (;;) {
-        kx.x = v.a;                                                   // 1. F = A K
-        HIP_TRY(launch_symv(st, kx, 1));
-        if ((rc = evaluate(0)) != GPMI_OK) return rc;
-        if (have_prev) {                                              // 2.
-            for (int halvings = 0;; ++halvings) {
-                const Step step = newton_decide(h[0], psi_prev, tol, halvings);
-                if (step != Step::Halve) { conv = step == Step::Converged; break; }
-                if ((rc = evaluate(1)) != GPMI_OK) return rc;
-            }
-        }
-        const bool last = conv || it >= max_iter;
-        // 3. per class: L_c = chol(I + s_c s_c^T o K) in A, V = S_c L_c^-T, -E_c = -V V^T (lower tiles)
-        HIP_TRY(launch_fill_rows(st, c->m_row(), ld, TILE, Np, 0.0));     // nothing rides in these factorisations
-        for (int k = 0; k < C; ++k) {
-            const double* sk = v.s + (int64_t)k * Np;
-            hipLaunchKernelGGL(softmax_bmat_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)K, A, ld, N, sk);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
-            c->res.factor_replaced(tuning().panel_fused);
-            HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * k));
-            HIP_TRY(launch_fill_rows(st, V, ld, Np, Np, 0.0));
-            hipLaunchKernelGGL(softmax_seed_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, V, ld, Np, sk);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(solve_sweep(c, V, ld, Np, true));
-            HIP_TRY(neg_gram_lower(c, V, nE + (int64_t)k * msize, ld, Np));
-        }
-        if (!last) {                                                  // 4. c_c = E_c (K b_c), sum_c c_c rides with M
-            kx.x = v.b;
-            HIP_TRY(launch_symv(st, kx, 1));
-            hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N,
-                               Np, C, 1.0, mat(SV_KB), (double*)nullptr);
-            HIP_TRY(hipGetLastError());
-            ex.x = mat(SV_KB); ex.xstride = Np;
-            HIP_TRY(launch_symv(st, ex, C));
-            hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N,
-                               Np, C, -1.0, mat(SV_CC), wv + SW_CSUM * Np);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(launch_set_yrow(st, c->m_row(), wv + SW_CSUM * Np, N, Np));
-        }
-        // 5. M = chol(sum_c E_c) in A
-        hipLaunchKernelGGL(softmax_esum_kernel, dim3(tiles), dim3(VEC_THREADS), 0, st, (const double*)nE, msize, C, A, ld, N);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(cholesky_inplace(c, A, ld, Np, c->Mp, c->info.as<int64_t>(), false));
-        c->res.factor_replaced(tuning().panel_fused);
-        HIP_TRY(launch_logdiag_sumsq(st, A, ld, N, nullptr, 0, zrec + 2 * C));
-        if (last) break;
-        double* x = nullptr;                                          // 6. t = M^-T M^-1 sum_c c_c, A <- B - C + [E_c t]
-        HIP_TRY(backward_solve_resident(c, wv + SW_X * Np, &x));
-        ex.x = x; ex.xstride = 0;
-        HIP_TRY(launch_symv(st, ex, C));
-        hipLaunchKernelGGL(softmax_update_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np,
-                           C, (const double*)mat(SV_CC), v);
-        HIP_TRY(hipGetLastError());
-        psi_prev = h[0];
-        have_prev = true;
-        ++it;
-    }
-    // prediction multiplies by the whole E_c
-    {
-        const int64_t nm = Np / MT;
-        hipLaunchKernelGGL(softmax_mirror_kernel, dim3((unsigned)(nm * (nm + 1) / 2), (unsigned)C), dim3(VEC_THREADS), 0, st,
-                           nE, msize, ld);
-        HIP_TRY(hipGetLastError());
-    }
+    bool conv = false;
+    if ((rc = newton_iterate(p, tol, max_iter, &it, &conv)) != GPMI_OK) return rc;
+    for (int k = 0; k < C; ++k)                                       // prediction multiplies by the whole E_c
+        HIP_TRY(launch_mirror_lower(st, p.nE + (int64_t)k * msize, ld, Np));
     std::vector<double> red(2 * (size_t)(C + 1));
     int64_t info = 0;
-    HIP_TRY(hipMemcpyAsync(red.data(), zrec, red.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(red.data(), p.zrec, red.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, st));
     if (f_hat)
-        HIP_TRY(hipMemcpy2DAsync(f_hat, (size_t)N * 8, v.f, (size_t)Np * 8, (size_t)N * 8, (size_t)C, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpy2DAsync(f_hat, (size_t)N * 8, p.v.f, (size_t)Np * 8, (size_t)N * 8, (size_t)C, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     c->timers_collect();
     if (info != NO_BAD_PIVOT) { g_err = std::string("gpmi_softmax_fit: ") + PIVOT_TEXT; return GPMI_ERR_NOT_PD; }
     // log q = Psi - sum_c sum log diag L_c - sum log diag M
     double z = 0.0;
     for (int k = 0; k < C; ++k) z += red[2 * (size_t)k];
-    if (log_q) *log_q = (h[0] - z) - red[2 * (size_t)C];
+    if (log_q) *log_q = (p.h[0] - z) - red[2 * (size_t)C];
     if (iters) *iters = it;
     if (converged) *converged = conv ? 1 : 0;
     c->sm_classes = C;
@@ -709,13 +686,11 @@ static int latent_cov(gpmi_ctx* c, const double* R, int64_t ldr, int64_t np, dou
     for (int k = 0; k < C; ++k) {                                     // B_c = R E_c = 0 - R (-E_c)^T
         HIP_TRY(launch_gemm_nt(st, gemm_minus(Bc + (int64_t)k * np * ldr, ldr, R, ldr, nE + (int64_t)k * msize, ld, np, Np, Np)));
     }
-    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, R, ldr, Np, (const double*)Bc,
-                       np * ldr, ldr, C, dd);                         // B_c[i] . R[i]
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_rowdot_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, R, ldr, Np, (const double*)Bc, np * ldr,
+               ldr, C, dd);                                           // B_c[i] . R[i]
     HIP_TRY(solve_sweep(c, Bc, ldr, C * np));                         // U_c^T = B_c M^-T, all classes in one sweep
-    hipLaunchKernelGGL(softmax_gram_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, (const double*)Bc, ldr, np, Np, C,
-                       c->sig2, (const double*)dd, cov);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_gram_kernel, dim3((unsigned)np), dim3(VEC_THREADS), 0, st, (const double*)Bc, ldr, np, Np, C, c->sig2,
+               (const double*)dd, cov);
     return GPMI_OK;
 }
 
@@ -728,13 +703,11 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     hipStream_t st = c->stream;
     const int C = c->sm_classes;
     const int64_t Np = c->Np, np_ = c->np_, n = c->n;
-    int rc;
-    c->res.drop_v();
-    c->ldV = Np + c->ld_pad;
-    const int64_t ldV = c->ldV;
-    HIP_TRY(c->V.ensure((size_t)np_ * ldV * 8));
+    const int64_t ldV = Np + c->ld_pad;                   // what predict_front makes c->ldV
     HIP_TRY(c->sm_B.ensure((size_t)C * np_ * ldV * 8));
     HIP_TRY(c->sm_out.ensure(((size_t)np_ * C * (3 + C) + (size_t)S * C) * 8));
+    int rc = predict_front(c, -1);                        // R = K(X*, X)
+    if (rc) return rc;
     double* R = c->V.as<double>();
     double* Bc = c->sm_B.as<double>();
     double* o_mu = c->sm_out.as<double>();
@@ -743,18 +716,13 @@ int softmax_predict_impl(gpmi_ctx* c, double* mu, double* cov, int64_t S, const 
     double* o_cov = o_prob + np_ * C;
     double* o_z = o_cov + np_ * C * C;
     const double* G = c->sm.as<double>() + (int64_t)SV_G * C * Np;
-
-    const RbfArgs r = rbf_test_train(c, R, ldV);          // R = K(X*, X)
-    HIP_TRY(launch_rbf(st, r));
-    hipLaunchKernelGGL(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,
-                       (int64_t)0, C, o_mu);                          // mu* = R (Y - P)^T
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_rowdot_kernel, dim3((unsigned)np_), dim3(VEC_THREADS), 0, st, (const double*)R, ldV, Np, G, Np,
+               (int64_t)0, C, o_mu);                                  // mu* = R (Y - P)^T
     if ((rc = latent_cov(c, R, ldV, np_, Bc, o_dd, o_cov)) != GPMI_OK) return rc;
     if (S > 0) {
         HIP_TRY(hipMemcpyAsync(o_z, normals, (size_t)S * C * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(softmax_sample_kernel, dim3((unsigned)n), dim3(VEC_THREADS), 0, st, C, S, (const double*)o_mu,
-                           (const double*)o_cov, (const double*)o_z, o_prob);
-        HIP_TRY(hipGetLastError());
+        LAUNCH_TRY(softmax_sample_kernel, dim3((unsigned)n), dim3(VEC_THREADS), 0, st, C, S, (const double*)o_mu,
+                   (const double*)o_cov, (const double*)o_z, o_prob);
     }
     if (mu) HIP_TRY(hipMemcpyAsync(mu, o_mu, (size_t)n * C * 8, hipMemcpyDeviceToHost, st));
     if (cov) HIP_TRY(hipMemcpyAsync(cov, o_cov, (size_t)n * C * C * 8, hipMemcpyDeviceToHost, st));
@@ -810,28 +778,20 @@ int softmax_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) 
     int rc;
 
     const size_t sp = c->span_begin(GPMI_T_GRAD);
-    {                                                                 // K whole: its rows are the R of latent_cov
-        const int64_t nm = Np / MT;
-        hipLaunchKernelGGL(softmax_mirror_kernel, dim3((unsigned)(nm * (nm + 1) / 2), 1u), dim3(VEC_THREADS), 0, st, K,
-                           (int64_t)0, ld);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(launch_mirror_lower(st, K, ld, Np));                      // K whole: its rows are the R of latent_cov
     if ((rc = latent_cov(c, K, ld, Np, Bc, dd, cov)) != GPMI_OK) return rc;                  // 1.
-    hipLaunchKernelGGL(softmax_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, C, F, (const double*)cov, s2);
-    HIP_TRY(hipGetLastError());                                                              // 2.
+    LAUNCH_TRY(softmax_s2_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, N, Np, C, F, (const double*)cov, s2);   // 2.
 
     SymvArgs kx;                                                                             // 3.
     kx.M = K; kx.mstride = 0; kx.ld = ld; kx.nt = nt; kx.x = s2; kx.xstride = 0; kx.nvec = C; kx.part = part;
     HIP_TRY(launch_symv(st, kx, 1));
-    hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
-                       1.0, ks2, (double*)nullptr);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C, 1.0, ks2,
+               (double*)nullptr);
     SymvArgs ex;
     ex.M = nE; ex.mstride = msize; ex.ld = ld; ex.nt = nt; ex.x = ks2; ex.xstride = Np; ex.nvec = 1; ex.part = part;
     HIP_TRY(launch_symv(st, ex, C));
-    hipLaunchKernelGGL(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
-                       -1.0, vv, vsum);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_vec_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C, -1.0, vv,
+               vsum);
     HIP_TRY(launch_fill_rows(st, U, ld, TILE, Np, 0.0));              // M^-1 sum_c v_c: row 0 of a one-tile sweep
     HIP_TRY(launch_set_yrow(st, U, vsum, N, Np));
     HIP_TRY(solve_sweep(c, U, ld, TILE));
@@ -840,9 +800,8 @@ int softmax_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) 
     HIP_TRY(backward_solve_rhs(c, x2, &t));
     ex.x = t; ex.xstride = 0;
     HIP_TRY(launch_symv(st, ex, C));
-    hipLaunchKernelGGL(softmax_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
-                       (const double*)s2, (const double*)vv, z);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_z_kernel, dim3(grid_of(Np)), dim3(VEC_THREADS), 0, st, (const double*)part, nt, N, Np, C,
+               (const double*)s2, (const double*)vv, z);
 
     HIP_TRY(launch_fill_rows(st, Bc, ld, Np, Np, 0.0));                                      // 4.
     for (int k = 0; k < C; ++k) {
@@ -850,39 +809,17 @@ int softmax_grad_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma) 
         HIP_TRY(solve_sweep(c, U, ld, Np));
         HIP_TRY(neg_gram_lower_dense(c, U, Bc, ld, Np));
     }
-    hipLaunchKernelGGL(softmax_weight_kernel, dim3(tiles), dim3(VEC_THREADS), (size_t)4 * C * LT * sizeof(double), st, nE,
-                       msize, C, Bc, ld, Np, G, (const double*)z);                           // 5.
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(softmax_weight_kernel, dim3(tiles), dim3(VEC_THREADS), (size_t)4 * C * LT * sizeof(double), st, nE, msize, C,
+               Bc, ld, Np, G, (const double*)z);                                             // 5.
 
     HIP_TRY(hipMemsetAsync(zero, 0, (size_t)Np * 8, st));                                    // 6.
     GradArdArgs ga;
     ga.Z = c->x_train(); ga.n = N; ga.d = c->d;
     ga.alpha = zero; ga.Kn = Bc; ga.ld = ld; ga.coef = c->coef;
     ga.family = 0;
-    const int64_t nblk = grad_ard_blocks(ga), nl = grad_ard_launches(ga), w = grad_ard_width(ga);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
-    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
-    ga.partial = c->gpart.as<double>();
-    ga.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_ard(st, ga));
-    c->span_end(sp);
-    std::vector<double> sums((size_t)nl * (size_t)(w + 3));
-    HIP_TRY(hipMemcpyAsync(sums.data(), ga.sums, sums.size() * 8, hipMemcpyDeviceToHost, st));
-    int gave_up = 0;
-    if (c->res.factor_fused && tuning().trsv_vinv >= 2)
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    c->timers_collect();
-    if (gave_up) return fail_gave_up("gpmi_softmax_grad");
-    // laplace_grad_impl's scaling: sum Wm K/sigma^2 e_k^2 per dimension, then the l and sigma sums (the noise slot is unused)
-    const double l2 = c->ell * c->ell;
-    if (d_r)
-        for (int64_t k = 0; k < c->d; ++k) {
-            const double rk = c->ard() ? c->ard_r[(size_t)k] : 1.0;
-            d_r[k] = .5 * (c->sig2 * sums[(size_t)((k / w) * (w + 3) + k % w)] / (l2 * rk));
-        }
-    if (d_ell) *d_ell = .5 * (c->sig2 * sums[(size_t)w] / (l2 * c->ell));
-    if (d_sigma) *d_sigma = .5 * (2 * c->sigma * sums[(size_t)w + 1]);
+    std::vector<double> sums;                             // backward_solve_rhs ran: its give-up word is read
+    if ((rc = grad_ard_finish(c, ga, sp, "gpmi_softmax_grad", &sums))) return rc;
+    grad_ard_scale(c, ga, sums, c->ell * c->ell, d_r, d_ell, d_sigma, nullptr);      // the noise slot is unused
     return GPMI_OK;
 }
 

@@ -538,12 +538,10 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
         HIP_TRY(solve_sweep_factor(c, Lm, ldm, mp, W, ldm, rows));       // row i <- A[:, i]^T
         c->span_end(sp);
         sp = c->span_begin(GPMI_T_MEANVAR);
-        hipLaunchKernelGGL(sparse_row_kernel, dim3((unsigned)rows), dim3(256), 0, st, W, ldm, mp, nreal, row0,
-                           (const double*)(c->y.as<double>() + row0), method, noise_var, c->sig2, c->sp_q.as<double>() + row0,
-                           yt, rpart, rows, bad);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sparse_sums_kernel, dim3(1), dim3(256), 0, st, (const double*)rpart, rows, acc);
-        HIP_TRY(hipGetLastError());
+        LAUNCH_TRY(sparse_row_kernel, dim3((unsigned)rows), dim3(256), 0, st, W, ldm, mp, nreal, row0,
+                   (const double*)(c->y.as<double>() + row0), method, noise_var, c->sig2, c->sp_q.as<double>() + row0,
+                   yt, rpart, rows, bad);
+        LAUNCH_TRY(sparse_sums_kernel, dim3(1), dim3(256), 0, st, (const double*)rpart, rows, acc);
         HIP_TRY(launch_gemv_t(st, W, ldm, rows, mp, yt, gs, c->sp_scr.as<double>()));
         HIP_TRY(launch_sum_fixed(st, gs, 1, mp, mp, g, 1.0, g));
         c->span_end(sp);
@@ -559,9 +557,8 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     HIP_TRY(cholesky_inplace(c, Bm, ldm, mp, mp + TILE, info + 1, false));
     c->span_end(sp);
     HIP_TRY(launch_lml_reduce(st, Bm, ldm, crow, m, red));
-    hipLaunchKernelGGL(sparse_value_kernel, dim3(1), dim3(64), 0, st, (const double*)acc, (const double*)red, (double)N,
-                       method, noise_var, rec);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(sparse_value_kernel, dim3(1), dim3(64), 0, st, (const double*)acc, (const double*)red, (double)N,
+               method, noise_var, rec);
     c->span_end(sp_all);
     double h_rec[8];
     HIP_TRY(hipMemcpyAsync(h_rec, rec, sizeof h_rec, hipMemcpyDeviceToHost, st));
@@ -703,14 +700,11 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
     HIP_TRY(inverse_transposed(c, Bm, ldm, mp, G0, ldm));                                            // G0 = L_B^-T
     HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, cvec, u, nullptr));       // u = L_B^-T c
     HIP_TRY(neg_product(G1, G0, G0, mp));                                  // G1 = -B^-1
-    hipLaunchKernelGGL(sparse_grad_scalars_kernel, dim3(1), dim3(256), 0, st, (const double*)G1, ldm, m,
-                       (const double*)c->sp_q.as<double>(), N, c->sig2, rec);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sparse_tril_kernel, egrid, dim3(256), 0, st, Bm, G0, ldm, mp);      // G0 = L_B
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(sparse_grad_scalars_kernel, dim3(1), dim3(256), 0, st, (const double*)G1, ldm, m,
+               (const double*)c->sp_q.as<double>(), N, c->sig2, rec);
+    LAUNCH_TRY(sparse_tril_kernel, egrid, dim3(256), 0, st, Bm, G0, ldm, mp);      // G0 = L_B
     HIP_TRY(neg_product(G2, G0, G0, mp));                                  // G2 = -B
-    hipLaunchKernelGGL(sparse_grad_core_kernel, egrid, dim3(256), 0, st, G2, G1, (const double*)u, ldm, mp, inv_s);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(sparse_grad_core_kernel, egrid, dim3(256), 0, st, G2, G1, (const double*)u, ldm, mp, inv_s);
     HIP_TRY(inverse_transposed(c, Lm, ldm, mp, G0, ldm));                                            // G0 = L^-T
     HIP_TRY(launch_row_dots(st, G0, ldm, mp, mp, u, p, nullptr));          // p = L^-T u
     HIP_TRY(neg_product(E, G0, G1, mp));
@@ -742,9 +736,8 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
         c->span_end(sp);
         sp = c->span_begin(GPMI_T_SOLVE_V);
         HIP_TRY(launch_row_dots(st, W, ldm, nreal, mp, p, dot, nullptr));
-        hipLaunchKernelGGL(sparse_beta_kernel, dim3(1), dim3(256), 0, st, (const double*)(c->y.as<double>() + row0),
-                           (const double*)dot, nreal, inv_s, beta, rec + 2);
-        HIP_TRY(hipGetLastError());
+        LAUNCH_TRY(sparse_beta_kernel, dim3(1), dim3(256), 0, st, (const double*)(c->y.as<double>() + row0),
+                   (const double*)dot, nreal, inv_s, beta, rec + 2);
         c->span_end(sp);
         sp = c->span_begin(GPMI_T_POSTCHOL);
         HIP_TRY(neg_product(E, W, G1, rows));                              // E = W T
@@ -754,9 +747,8 @@ int sparse_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_nois
         HIP_TRY(launch_contract(st, ca, colF));
         c->span_end(sp);
     }
-    hipLaunchKernelGGL(sparse_grad_final_kernel, dim3(1), dim3(256), 0, st, (const double*)colF, (const double*)colU, m, mp,
-                       d, rec + 3, dz);
-    HIP_TRY(hipGetLastError());
+    LAUNCH_TRY(sparse_grad_final_kernel, dim3(1), dim3(256), 0, st, (const double*)colF, (const double*)colU, m, mp,
+               d, rec + 3, dz);
     c->span_end(sp_all);
     std::vector<double> h((size_t)(nrec + m * d));
     HIP_TRY(hipMemcpyAsync(h.data(), rec, (d_Z ? h.size() : (size_t)nrec) * 8, hipMemcpyDeviceToHost, st));

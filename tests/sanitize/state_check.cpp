@@ -1,15 +1,21 @@
-// TEST INFRASTRUCTURE: Resident and newton_decide (gaussian_process_amd/csrc/gpmi_state.h) asked from the command line,
+// TEST INFRASTRUCTURE: Resident, newton_decide and newton_iterate (gaussian_process_amd/csrc/gpmi_state.h) asked from the command line,
 // built with g++ -fsanitize=address,undefined by tests/test_state_cpu.py.
 //   state_check events   one event name of tests/state_table.py per line of standard input ("reset": a fresh context);
 //                        each is applied through the transitions the library's entry point of that name goes through,
 //                        and answered by one line: the consumer groups the state then accepts ("-": none)
 //   state_check newton   one "psi psi_prev tol halvings" per line (hex floats); the answer is newton_decide's
-// An unknown word prints FAIL and exits non-zero.
+//   state_check iterate  one run of newton_iterate per line: "tol max_iter fail nth status psi ..." (hex floats); the
+//                        psi are what the problem's evaluate reports, call by call; the nth call (from 1) of the
+//                        callback `fail` (forward, eval, factor or step; "-": none) returns `status`.  The answer is
+//                        the trace of calls (forward, eval0, eval1, factor0, factor1, step), then iters, converged and
+//                        the status (iters and converged are -1 where newton_iterate left them alone)
+// An unknown word, or a run that asks for more psi than its line holds, prints FAIL and exits non-zero.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "gpmi_state.h"
 
@@ -73,6 +79,29 @@ static void answer(const Resident& r) {
     std::puts(out.empty() ? "-" : out.c_str());
 }
 
+// newton_iterate's problem from a script: every callback appends its name to the trace
+struct ScriptedProblem {
+    std::vector<double> psi;
+    size_t next = 0;
+    std::string fail;
+    int nth = 0, status = 0;
+    int calls[4] = {0, 0, 0, 0};
+    std::string trace;
+
+    int called(int which, const char* name, const std::string& shown) {
+        trace += shown + " ";
+        return fail == name && ++calls[which] == nth ? status : 0;
+    }
+    int forward() { return called(0, "forward", "forward"); }
+    int evaluate(int mode, double* out) {
+        if (next == psi.size()) { std::printf("FAIL: the script ran out of psi after: %s\n", trace.c_str()); std::exit(1); }
+        *out = psi[next++];
+        return called(1, "eval", mode ? "eval1" : "eval0");
+    }
+    int factor(bool last) { return called(2, "factor", last ? "factor1" : "factor0"); }
+    int step() { return called(3, "step", "step"); }
+};
+
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     std::string line;
@@ -97,6 +126,21 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
-    std::printf("FAIL: mode must be events or newton\n");
+    if (mode == "iterate") {
+        while (std::getline(std::cin, line)) {
+            std::istringstream in(line);
+            std::string tol, word;
+            int max_iter = 0;
+            ScriptedProblem p;
+            if (!(in >> tol >> max_iter >> p.fail >> p.nth >> p.status)) { std::printf("FAIL: %s\n", line.c_str()); return 1; }
+            while (in >> word) p.psi.push_back(std::strtod(word.c_str(), nullptr));
+            int iters = -1;
+            bool converged = false;
+            const int rc = newton_iterate(p, std::strtod(tol.c_str(), nullptr), max_iter, &iters, &converged);
+            std::printf("%s%d %d %d\n", p.trace.c_str(), iters, iters < 0 ? -1 : (int)converged, rc);
+        }
+        return 0;
+    }
+    std::printf("FAIL: mode must be events, newton or iterate\n");
     return 1;
 }

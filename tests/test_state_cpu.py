@@ -1,9 +1,10 @@
-"""The resident-state rule (state_table.py) and the Newton step decision of the classifiers' mirrors against the one
-header that holds both for the library (gaussian_process_amd/csrc/gpmi_state.h), under g++ AddressSanitizer + UBSan.
-No GPU.
+"""The resident-state rule (state_table.py), the Newton step decision and the Newton loop of the classifiers' mirrors
+against the one header that holds all three for the library (gaussian_process_amd/csrc/gpmi_state.h), under g++
+AddressSanitizer + UBSan.  No GPU.
 
 tests/sanitize/state_check.cpp replays event names through the header's transitions and prints what the state then
-accepts; in its second mode it answers newton_decide for (psi, psi_prev, tol, halvings)."""
+accepts; in its second mode it answers newton_decide for (psi, psi_prev, tol, halvings); in its third it runs
+newton_iterate on a scripted objective and prints the calls the loop made."""
 import os
 import shutil
 import subprocess
@@ -110,3 +111,76 @@ def test_newton_decide_at_its_boundaries(state_check):
     got = state_check("newton", [q for q, _ in cases])
     wrong = ["%s: want %s, newton_decide %s" % (q, w, g) for (q, w), g in zip(cases, got) if g != w]
     assert not wrong, "\n".join(wrong)
+
+
+def run_line(tol, max_iter, psis, fail="-", nth=0, status=0):
+    return "%s %d %s %d %d %s" % (hexf(tol), max_iter, fail, nth, status, hexf(*psis))
+
+
+TOL = 2.0 ** -10         # of the scripted runs: the threshold tol max(1, |Psi|) stays under 1 for every |Psi| below 1024
+
+
+def parse_run(line):
+    """-> (trace words, iters, converged, status)"""
+    words = line.split()
+    return words[:-3], int(words[-3]), int(words[-2]), int(words[-1])
+
+
+def test_newton_iterate_by_hand(state_check):
+    halve20 = ["forward", "eval0"] + ["eval1"] * 20 + ["factor0", "step"]
+    cases = [
+        # max_iter = 0: one evaluation, the factor of the start, nothing else
+        (run_line(TOL, 0, [3.0]), ("forward eval0 factor1".split(), 0, 0, 0)),
+        # the first comparison (there is none before the first step) converges: the last factor, no step behind it
+        (run_line(TOL, 5, [-10.0, -10.0 - 2.0 ** -7]), ("forward eval0 factor0 step forward eval0 factor1".split(), 1, 1, 0)),
+        # the cap: rising all the way, max_iter steps and the factor of iterate max_iter
+        (run_line(TOL, 2, [-10.0, -5.0, -2.0]),
+         ("forward eval0 factor0 step forward eval0 factor0 step forward eval0 factor1".split(), 2, 0, 0)),
+        # ... and converging exactly at the cap counts as converged
+        (run_line(TOL, 1, [-10.0, -10.0]), ("forward eval0 factor0 step forward eval0 factor1".split(), 1, 1, 0)),
+        # one halving: the halved step's Psi is the one the next comparison is made against (-8 -> -8 - 2^-8 converges,
+        # which it would not against -20 or -10)
+        (run_line(TOL, 9, [-10.0, -20.0, -8.0, -8.0 - 2.0 ** -8]),
+         ("forward eval0 factor0 step forward eval0 eval1 factor0 step forward eval0 factor1".split(), 2, 1, 0)),
+        # twenty halvings of a step that keeps falling, then it is accepted as it is
+        (run_line(TOL, 9, [0.0] + [-10.0 - k for k in range(21)] + [-30.0]),
+         ("forward eval0 factor0 step".split() + halve20 + "forward eval0 factor1".split(), 2, 1, 0)),
+        # a status from each callback ends the run there, with that status and nothing reported
+        (run_line(TOL, 9, [0.0, 5.0], "forward", 1, 7), (["forward"], -1, -1, 7)),
+        (run_line(TOL, 9, [0.0, 5.0], "forward", 2, 7), ("forward eval0 factor0 step forward".split(), -1, -1, 7)),
+        (run_line(TOL, 9, [0.0, 5.0], "eval", 1, 3), ("forward eval0".split(), -1, -1, 3)),
+        (run_line(TOL, 9, [0.0, -5.0, -4.0], "eval", 3, 3), ("forward eval0 factor0 step forward eval0 eval1".split(), -1, -1, 3)),
+        (run_line(TOL, 9, [0.0, 5.0], "factor", 1, 2), ("forward eval0 factor0".split(), -1, -1, 2)),
+        (run_line(TOL, 0, [0.0], "factor", 1, 2), ("forward eval0 factor1".split(), -1, -1, 2)),
+        (run_line(TOL, 9, [0.0, 5.0], "step", 1, 1), ("forward eval0 factor0 step".split(), -1, -1, 1)),
+        (run_line(TOL, 9, [0.0, 5.0, 9.0], "step", 2, -4),
+         ("forward eval0 factor0 step forward eval0 factor0 step".split(), -1, -1, -4)),
+    ]
+    got = [parse_run(g) for g in state_check("iterate", [q for q, _ in cases])]
+    wrong = ["%s: want %s, newton_iterate %s" % (q, w, g) for (q, w), g in zip(cases, got) if g != w]
+    assert not wrong, "\n".join(wrong)
+
+
+def test_newton_iterate_takes_the_mirrors_runs(state_check):
+    """a Psi script from the full run of every step-halving problem: after each Newton step halvings[k] values that keep
+    falling, then one that rises (the step is accepted) -- after the last step one that repeats the previous iterate's
+    (converged).  The loop must halve as often per step as the mirror did and report its iters and converged."""
+    lines, want = [], []
+    for kind in H.KINDS:
+        ref = H.reference(kind, "full")
+        assert ref["converged"] and len(ref["halvings"]) == ref["iters"] and sum(ref["halvings"]) >= 2
+        psis, prev = [0.0], 0.0
+        for k, nh in enumerate(ref["halvings"]):
+            psis += [prev - 8.0 - i for i in range(nh)]
+            prev = prev if k + 1 == len(ref["halvings"]) else prev + 8.0
+            psis.append(prev)
+        lines.append(run_line(TOL, H.max_iter_of(kind, "full"), psis))
+        want.append((list(ref["halvings"]), ref["iters"], int(ref["converged"]), 0))
+    got = []
+    for line in state_check("iterate", lines):
+        trace, iters, converged, status = parse_run(line)
+        runs = " ".join(trace).split("forward")[1:]                 # one piece per forward product
+        assert all(r.split()[0] == "eval0" and r.split().count("eval0") == 1 for r in runs), trace
+        assert [r.split()[-1] for r in runs] == ["step"] * (len(runs) - 1) + ["factor1"], trace
+        got.append(([r.split().count("eval1") for r in runs[1:]], iters, converged, status))
+    assert got == want
