@@ -7,6 +7,7 @@
 #include <cmath>
 #include <mutex>
 
+#include "gpmi_kroute.h"
 #include "gpmi_route.h"
 
 namespace gpmi {
@@ -163,8 +164,8 @@ struct RbfArgs {
 hipError_t launch_rbf(hipStream_t s, const RbfArgs& a);
 // The stationary kinds share the register-path K build and the gradient kernels, which take the per-element function
 // as a compile-time family: 0 squared exponential, 1 / 2 / 3 Matern nu = 1/2, 3/2, 5/2 (kinds 4 / 5 / 6).
-inline int cov_family(int kind) { return (kind >= 4 && kind <= 6) ? kind - 3 : 0; }
-inline bool cov_stationary(int kind) { return kind == 0 || cov_family(kind) != 0; }
+inline int cov_family(int kind) { return rbf_family(kind); }                   // gpmi_kroute.h
+inline bool cov_stationary(int kind) { return rbf_stationary(kind); }
 // what multiplies sq (family 0: GP_regression.py:19 evaluation order) or sqrt(sq) (Matern: -a) in the exp argument
 inline double cov_coef(int kind, double ell) {
     static const double two_nu[4] = {0.0, 1.0, 3.0, 5.0};

@@ -35,8 +35,8 @@ namespace gpmi {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-constexpr int RT = 128;        // tile edge
-constexpr int LDS_MAXD = 32;   // largest d staged in LDS; above: rbf_naive_kernel
+constexpr int RT = RBF_TILE;           // tile edge
+constexpr int LDS_MAXD = RBF_LDS_MAXD; // largest d staged in LDS; above: rbf_naive_kernel
 
 struct RbfDev {
     const double* __restrict__ A;
@@ -103,8 +103,10 @@ __device__ __forceinline__ void exp_pair(double x0, double x1, double& e0, doubl
 // the polynomial-only form above (the K build is bound by its instruction count):
 // one multiply-add for k and j at once, a two-term Cody-Waite reduction, two instructions each for the table
 // address and for the exponent, three for the cubic, one for T + T q.  T[0] == 1 and r == 0 at x == 0, so
-// exp(0) == 1 exactly and the diagonal of K stays sigma^2.  Error: 0.5 ulp of the table entry + 0.5 ulp of the
-// final fused multiply-add (measured: scripts/exp_accuracy.py).  Same domain as exp_neg_fast.
+// exp(0) == 1 exactly and the diagonal of K stays sigma^2.  Error <= 1.03 ulp: 0.501 ulp of the table entry + 0.5 ulp of the
+// final fused multiply-add + 0.02 of the truncation; tests/kbuild_ref.py emulates this function exactly (1.010 ulp the worst
+// found over its directed arguments) and tests/test_kbuild_routes_gpu.py holds the device to the emulation bit for bit, so a
+// change of any constant or operation here has to be made there too.  Same domain as exp_neg_fast.
 constexpr int EXP_TAB = 4096;
 constexpr int EXP_TAB_LOG = 12;
 __device__ double g_exp2_tab[EXP_TAB];
@@ -193,11 +195,7 @@ __device__ double sq_pw_global(const double* a, const double* b, int n) {
 
 __device__ __forceinline__ bool rbf_map_tile(const RbfDev& p, int& ti, int& tj) {
     if (p.tri) {
-        const int s = blockIdx.x;
-        ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
-        while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
-        while (ti * (ti + 1) / 2 > s) --ti;
-        tj = s - ti * (ti + 1) / 2;
+        rbf_tri_tile((int)blockIdx.x, ti, tj);      // gpmi_kroute.h
     } else {
         ti = blockIdx.x / p.Tn;
         tj = blockIdx.x - ti * p.Tn;
@@ -541,55 +539,51 @@ static hipError_t exp_table_ready() {
     });
 }
 
+// Which kernel, with what geometry: rbf_route (gpmi_kroute.h) decides, this function launches its answer.
 hipError_t launch_rbf(hipStream_t s, const RbfArgs& a) {
-    if (a.nrows <= 0 || a.ncols <= 0) return hipSuccess;
-    if (a.nrows % RT || a.ncols % RT || a.d <= 0) return hipErrorInvalidValue;
-    if (a.symmetric && a.row0 % RT) return hipErrorInvalidValue;
+    const RbfRoute rt = rbf_route(a.kind, a.d, a.nrows, a.ncols, a.symmetric, a.row0, a.coef, a.max_sq, tuning().rbf_blocks);
+    if (rt.kernel == RbfKernel::Nothing) return hipSuccess;
+    if (rt.kernel == RbfKernel::Invalid) return hipErrorInvalidValue;
     RbfDev p;
     p.A = a.A; p.B = a.B; p.nA = a.nA; p.nB = a.nB; p.d = (int)a.d; p.row0 = a.row0;
-    p.Tm = (int)(a.nrows / RT); p.Tn = (int)(a.ncols / RT);
+    p.Tm = rt.Tm; p.Tn = rt.Tn;
     p.coef = a.coef; p.sig2 = a.sig2; p.diag_add = a.diag_add; p.symmetric = a.symmetric;
     p.out = a.out; p.ld = a.ld;
     p.kind = a.kind; p.kp0 = a.kp0; p.kp1 = a.kp1;
     for (int i = 0; i < 11; ++i) p.kpv[i] = a.kpv[i];
     p.delta_square = a.delta_square;
     p.delta_col0 = a.delta_col0;
-    if (a.kind < 0 || a.kind > 6 || (a.kind == 2 && a.d != 1)) return hipErrorInvalidValue;
-    const int fam = cov_family(a.kind);
-    // coef <= 0 and max_sq bounds every squared distance of this launch (NaN / unknown fail the test); a Matern's
-    // argument is coef * sqrt(sq)
-    const double max_arg = fam ? a.coef * std::sqrt(a.max_sq) : a.coef * a.max_sq;
-    p.nocheck = (a.max_sq >= 0.0 && a.coef <= 0.0 && max_arg * 1.000001 >= -690.0) ? 1 : 0;
-    p.tri = (a.symmetric && a.row0 == 0 && p.Tm == p.Tn) ? 1 : 0;
-    const int64_t nblk = p.tri ? (int64_t)p.Tm * (p.Tm + 1) / 2 : (int64_t)p.Tm * p.Tn;
-    dim3 grid((unsigned)nblk), block(256);
-    const size_t lds = (size_t)2 * RT * a.d * sizeof(double);
-    if (!cov_stationary(a.kind)) {
-        // lin / per / CO2 composite: the LDS-staged tile kernel (d <= 32), straight from global memory above that
-        if (a.d <= LDS_MAXD) hipLaunchKernelGGL(rbf_kernel<0>, grid, block, lds, s, p);
-        else hipLaunchKernelGGL(cov_other_kernel, grid, block, 0, s, p);
+    p.nocheck = rt.nocheck;
+    p.tri = rt.tri;
+    p.strip = rt.strip;
+    p.nitems = rt.nitems;
+    const dim3 grid(rt.grid), block(256);
+    if (rt.kernel == RbfKernel::Other) {
+        hipLaunchKernelGGL(cov_other_kernel, grid, block, 0, s, p);
+        return hipGetLastError();
+    }
+    if (!cov_stationary(a.kind)) {              // lin / per / CO2 composite up to d = 32: the LDS-staged tile kernel
+        hipLaunchKernelGGL(rbf_kernel<0>, grid, block, rt.lds, s, p);
         return hipGetLastError();
     }
     {
         const hipError_t et = exp_table_ready();
         if (et != hipSuccess) return et;
     }
-    // big builds: 4 row tiles per block (b columns loaded once, 4x fewer block launches)
-    p.strip = (nblk >= 4096) ? 4 : 1;
-    p.nitems = p.Tn * ((p.Tm + p.strip - 1) / p.strip);
-    const dim3 sgrid((unsigned)std::min<int64_t>(p.nitems, tuning().rbf_blocks));
-#define RBF_CASE(DD, FF) case DD: hipLaunchKernelGGL((rbf_regs_kernel<DD, FF>), sgrid, block, 0, s, p.A, p.B, p.out, p); break
+#define RBF_CASE(DD, FF) case DD: hipLaunchKernelGGL((rbf_regs_kernel<DD, FF>), grid, block, 0, s, p.A, p.B, p.out, p); break
 #define RBF_FAMILY(FF)                                                                                                 \
-    if (a.d > LDS_MAXD) {                                                                                              \
+    if (rt.kernel == RbfKernel::Naive) {                                                                               \
         hipLaunchKernelGGL(rbf_naive_kernel<FF>, grid, block, 0, s, p);                                                \
+    } else if (rt.kernel == RbfKernel::Lds) {                                                                          \
+        hipLaunchKernelGGL((rbf_kernel<0, FF>), grid, block, rt.lds, s, p);                                            \
     } else {                                                                                                           \
-        switch (a.d) {                                                                                                 \
+        switch (rt.D) {                                                                                                \
             RBF_CASE(1, FF); RBF_CASE(2, FF); RBF_CASE(3, FF); RBF_CASE(4, FF); RBF_CASE(5, FF); RBF_CASE(6, FF);      \
             RBF_CASE(7, FF); RBF_CASE(8, FF); RBF_CASE(16, FF);                                                        \
-            default: hipLaunchKernelGGL((rbf_kernel<0, FF>), grid, block, lds, s, p); break;                           \
+            default: return hipErrorInvalidValue;       /* rbf_regs_d and this list name the same d */                 \
         }                                                                                                              \
     }
-    switch (fam) {
+    switch (rt.family) {
         case 0: RBF_FAMILY(0) break;
         case 1: RBF_FAMILY(1) break;
         case 2: RBF_FAMILY(2) break;
