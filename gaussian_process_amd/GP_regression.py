@@ -176,6 +176,14 @@ def prediction(X_train, X_test, y_train, kernel_choice, l, num_fun, *, sigma=SIG
     return mu_post, stand_devi, f_post_fun
 
 
+def append_observations(X_new, y_new, *, ctx=None):
+    """Add observations to the regression fit resident in ctx (the one prediction() or ctx.fit() left) without refitting:
+    O(N^2 k) instead of O(N^3).  Returns the log-marginal-likelihood of all points; predictions, gradients and
+    leave-one-out calls then see the extended fit."""
+    ctx = ctx or default_context()
+    return ctx.append(X_new, y_new)
+
+
 def f_prior(X_test, mu_prior, kernel_choice, kernel_parameter, num_fun, *, ctx=None):
     """GP prior samples, reference GP_regression.py:71-92 (s = 0.0005, sigma = 1).  With a Matern kernel_choice the
     parameter is l, a scalar or a d-vector."""

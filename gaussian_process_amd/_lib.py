@@ -50,6 +50,8 @@ SIGNATURES = {
     "gpmi_set_train": [_vp, _dp, _i64, _i64, _dp],
     "gpmi_factorize": [_vp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64)],
     "gpmi_fit": [_vp, _dp, _i64, _i64, _dp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64)],
+    "gpmi_append": [_vp, _dp, _i64, _dp, _dp, C.POINTER(_i64)],
+    "gpmi_get_layout": [_vp, C.POINTER(_i64)],
     "gpmi_get_alpha": [_vp, _dp],
     "gpmi_get_m": [_vp, _dp],
     "gpmi_get_diag": [_vp, _dp],
@@ -97,6 +99,7 @@ SIGNATURES = {
     "gpmi_dev_cov_cross": [_vp, C.c_int, _dp, C.c_int, _vp, _i64, _vp, _i64, _i64, _i64, C.c_int, _i64, _i64, _vp, _i64],
     "gpmi_dev_potrf_block": [_vp, _vp, _i64, _i64, _i64, _vp],
     "gpmi_dev_trsm_block": [_vp, _vp, _i64, _vp, _i64, _i64, _i64],
+    "gpmi_dev_border_sweep": [_vp, _vp, _i64, _i64, _vp, _i64, _i64],
     "gpmi_dev_gemm_nt": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int, _i64],
     "gpmi_dev_gemm_nt_rowmap": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64],
     "gpmi_dev_gemm_nt_rowmap_host": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64],

@@ -242,10 +242,13 @@ RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld) {
 
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows, bool test_cols) {
     c->Np = round_up(c->N, TILE);
-    c->ldA = c->Np + (test_cols ? test_rows : 0) + c->ld_pad;
-    c->Mp = c->Np + TILE + test_rows;
+    // option "reserve": columns and rows for that many more points, which gpmi_append then fills in place (0: cap == Np)
+    const int64_t cap = round_up(c->N + c->reserve, TILE);
+    c->ldA = cap + (test_cols ? test_rows : 0) + c->ld_pad;
+    c->Mp = c->Np + TILE + test_rows;              // the rows a factorisation carries: never the reserve's
+    c->rows_cap = cap + TILE + test_rows;          // the rows A has (the append plan's capacity)
     c->yrow = test_cols ? c->Np + test_rows : c->Np;         // with their own columns the test rows come BEFORE the y rows
-    HIP_TRY(c->A.ensure((size_t)c->Mp * c->ldA * sizeof(double)));
+    HIP_TRY(c->A.ensure((size_t)c->rows_cap * c->ldA * sizeof(double)));
     HIP_TRY(c->info.ensure(sizeof(int64_t)));
     HIP_TRY(c->red.ensure(16 * sizeof(double)));
     return GPMI_OK;

@@ -10,6 +10,8 @@
 //       on whole tiles.  Row Np carries y: the factorisation treats it as one
 //       more row of the panel, so when it finishes that row holds
 //       m = L^-1 y (forward substitution folded into the sweep, no extra pass).
+//       Option "reserve" r sizes both dimensions for N + r points instead; gpmi_append then
+//       grows the factor in place and moves the y row to the new Np (append.hip).
 //   V   n_p x ldV          row-major, row i = K(x*_i, X) then (L^-1 K_s)[:, i]
 //       (v transposed: both GEMM operands of the sweep stay K-contiguous).
 //   P   n_p x ldP          posterior covariance / its factor (gpmi_post_chol).
@@ -95,7 +97,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->app, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
                        &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred,
                        &c->sp_g0, &c->sp_g1, &c->sp_g2, &c->sp_gE, &c->sp_gpart, &c->sp_gvec})
         b->release();
@@ -178,6 +180,13 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "sparse_slab")) {
         if (value < 0) return fail_arg("sparse_slab must be >= 0 (0: by size)");
         c->sparse_slab = value;
+    } else if (!strcmp(name, "reserve")) {
+        // takes effect with the next fit; a resident one keeps the layout it was made with
+        if (value < 0) return fail_arg("reserve must be >= 0 (points that gpmi_append may add in place)");
+        c->reserve = value;
+    } else if (!strcmp(name, "append_skinny")) {
+        if (value < -1 || value > 1) return fail_arg("append_skinny must be -1 (by size), 0 (never) or 1 (whenever allowed)");
+        c->append_skinny = (int)value;
     } else if (!strcmp(name, "lanes")) {
         if (value < 0 || value > 8) return fail_arg("lanes must be 0 (by size) .. 8");
         c->lanes = (int)value;
@@ -375,6 +384,26 @@ int gpmi_fit(gpmi_ctx* c, const double* X, int64_t N, int64_t d, const double* y
     int rc = gpmi_set_train(c, X, N, d, y);
     if (rc) return rc;
     return gpmi_factorize(c, sigma, ell, noise_var, lml, bad_pivot);
+}
+
+// k more observations into the resident regression factorisation: the border of the factor, not a new fit (append.hip).
+// It solves and factors with the kind of leaves that produced the resident factor, so the factor stays of one kind.
+int gpmi_append(gpmi_ctx* c, const double* Xnew, int64_t k, const double* ynew, double* lml, int64_t* bad_pivot) {
+    if (!c) return fail_arg("gpmi_append: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    return append_impl(c, Xnew, k, ynew, lml, bad_pivot);
+}
+
+int gpmi_get_layout(gpmi_ctx* c, int64_t* out5) {
+    if (!c || !out5) return fail_arg("gpmi_get_layout: null argument");
+    out5[0] = c->res.have_train ? c->N : 0;
+    out5[1] = c->Np;
+    out5[2] = c->ldA;
+    out5[3] = c->rows_cap;
+    out5[4] = c->append_route;
+    return GPMI_OK;
 }
 
 int gpmi_get_m(gpmi_ctx* c, double* m_out) {

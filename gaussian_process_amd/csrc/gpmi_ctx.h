@@ -81,6 +81,19 @@ struct Box {
             }
         valid = finite;
     }
+    // the box of the set with n more points (gpmi_append)
+    void extend(const double* X, int64_t n, int64_t d) {
+        if ((int64_t)lo.size() != d) { assign(X, n, d); return; }
+        bool finite = valid;
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t k = 0; k < d; ++k) {
+                const double v = X[i * d + k];
+                finite &= std::isfinite(v);
+                lo[(size_t)k] = std::min(lo[(size_t)k], v);
+                hi[(size_t)k] = std::max(hi[(size_t)k], v);
+            }
+        valid = finite;
+    }
 };
 // The box of z = x / r from the box of x: division by a positive number is monotone under rounding, so the same
 // division the device performs on every element gives exact bounds of the scaled set.
@@ -132,9 +145,13 @@ struct gpmi_ctx {
     std::vector<gpmi_ctx*> lane_ctx;   // the extra lanes (own streams and workspaces), created on demand
     int ramp = 0;           // block-width schedule, bit mask: 1 ramp up at the start, 2 half width over the last blocks (count in bits 4.., default 3),
                             // 4 quarter width for the last block (measured: ramp up 0.4 % slower at N = 65536; ramp down within noise at N = 16384 / 32768: off)
+    int64_t reserve = 0;    // ensure_train_buffers sizes A for N + reserve points, so that gpmi_append stays in place
+    int append_route = -1;  // the route the last gpmi_append took: 1 skinny, 0 padded (gpmi_get_layout)
+    int append_skinny = -1; // gpmi_append, k <= 16 on a fused factor: -1 by size, 0 the padded 128-row sweep, 1 the <= 16-row kernel
     gpmi::Tuning tune;      // kernel-selection options of this context (installed per call: gpmi::TuneScope)
     // training set / factor
     int64_t N = 0, d = 0, Np = 0, ldA = 0, Mp = 0;
+    int64_t rows_cap = 0;    // rows A is laid out for (>= Mp, the rows in use: option "reserve", or what an append left)
     gpmi::Resident res;      // what is resident and what was derived from it: gpmi_state.h, the only place that changes it
     double sig2 = 1.0, coef = -0.5;
     int kind = 0;            // covariance function: 0 rbf, 1 linear, 2 periodic, 3 CO2 composite, 4 / 5 / 6 Matern nu = 1/2, 3/2, 5/2 (gpmi_set_kernel*)
@@ -171,6 +188,7 @@ struct gpmi_ctx {
     DevBuf gsum;             // gpmi_lml_grad_ard: the d + 3 sums, reduced on the device
     double sigma = 1.0, ell = 1.0;   // hyper-parameters of the resident factorisation
     double noise = 0.0;              // ... and its noise variance (regression factorisations only)
+    DevBuf app;              // gpmi_append, skinny route: the new points (aligned copy) and their 128 x N0 rows of K
     DevBuf loov, loow;       // gpmi_loo / gpmi_loo_grad: the per-point vectors; the NB x ld row block of K_y^-1 D
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
@@ -285,6 +303,8 @@ RbfArgs rbf_sym(const gpmi_ctx* c, const double* X, int64_t n, const Box& box, d
                 int64_t ld);
 RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld);      // K(X*, X), n_p x Np
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows = 0, bool test_cols = false);
+// append.hip: k more observations into the resident regression factorisation (include/gpmi.h: gpmi_append)
+int append_impl(gpmi_ctx* c, const double* Xnew, int64_t k, const double* ynew, double* lml, int64_t* bad_pivot);
 // with_test: the test set's rows K(X*, X) ride below the y rows (they come out as v^T = K_s^T L^-T, a7 inside a3) and
 // mean / variance (a6, a8) are read off them behind the LML
 // with_post (needs with_test): the test rows also get their own columns K_ss + jitter I, i.e. ONE Cholesky of

@@ -133,6 +133,12 @@ hipError_t launch_potrf128(hipStream_t s, double* A, int64_t ld, int64_t col_off
 // X (m x 128) <- X * L^-T, L 128 x 128 lower; m multiple of 128; on the matrix pipe.
 hipError_t launch_trsm128(hipStream_t s, const double* L, int64_t ldl, double* X, int64_t ldx, int64_t m);
 
+// X (rows <= 16, ncols) <- X * L^-T for a fused factor L (ncols x ncols, ncols a multiple of 128): the forward sweep for
+// a few rows, one launch per 128 columns, L streamed once.  Rows of X from `rows` on and columns from ncols on are neither
+// read nor written; of L it reads what trsm128 reads, block by block.
+hipError_t launch_border_sweep(hipStream_t s, const double* L, int64_t ldl, int64_t ncols, double* X, int64_t ldx,
+                               int64_t rows);
+
 // ---- rbf.hip ---------------------------------------------------------------
 struct RbfArgs {
     const double* A;   // rows of the output: nA x d (row-major, device)

@@ -59,6 +59,10 @@ struct Resident {
     void train_set() { have_train = true; }
     void test_set() { have_test = true; }
     void factor_replaced(int fused) { have_vinv = have_vside = false; factor_fused = fused; }   // after any Cholesky into A
+    // gpmi_append: the regression factor grew by a border.  The fit stays; the border's diagonal blocks are new, so the
+    // next backward solve inverts again; v belongs to the shorter factor and goes, and the riding posterior factor with
+    // it (one cached in P is tied to its v by v_gen: the next v_computed() outdates it)
+    void factor_extended(int fused) { factor_replaced(fused); drop_v(); post_in_A = false; }
     void block_inverses_made(bool side) { have_vinv = true; have_vside = side; }
     void fit_done(Fit f) { fit = f; }
     void drop_v() { have_v = v_in_A = false; }                             // a prediction is about to overwrite V

@@ -562,9 +562,115 @@ __global__ __launch_bounds__(256, 2) void vinv128_kernel(double* A, int64_t ld, 
     }
 }
 
+// ---------------------------------------------------------------------------
+// border_sweep: X (rows <= 16, ncols) <- X * L^-T for a fused factor L (ncols x ncols), the forward sweep of gpmi_append
+// for a few new points.  trsm128's recurrence, but the work is reading L (streamed once; the flops are nothing), so
+// the grid follows the rows of L: the <= 16 rows of X are the B operand of every MFMA (dead rows fed as zeros, never
+// stored), 16 rows of L the A operand, read straight from memory in fragment layout (two 16-byte pieces of a row per
+// lane; the four lane groups take a row's 128 bytes between them), and one wave turns a 16 x 128 strip of L into the
+// update of a 16 x 16 piece of X.
+// One launch per 128-column block t, nblk - t workgroups: workgroup b updates column block t + b of X with the block
+// solved by the launch before, X_c -= X_(t-1) L_(c, t-1)^T, wave w its tiles w and 4 + w; workgroup 0 then solves its
+// block against L_tt (staged as in trsm128; one wave, 36 tile products), so launch t + 1 finds X_t final.  The order is
+// the launch order; no workgroup waits for another, nothing is added atomically: the same bits every run.
+// Measured (profiles/r14_append_rate.txt) the chain of launches bounds it, not memory: 12.8 us per launch at 4096
+// columns, where there is next to nothing to stream, 15.5 us and 0.35 of the streaming-read rate at 65536.  Not measured:
+// how the 12.8 us split between the launch gap and workgroup 0's update and one-wave solve, and what the LDS request adds
+// to the rest -- every workgroup asks for SWEEP_LDS though only workgroup 0 uses it, which holds the streaming
+// workgroups to one per CU.
+// Reads of L: the tiles below the block diagonal, and of the diagonal 128 x 128 blocks the lower 16 x 16 tiles and the
+// diagonal tiles whole (their stored inverses) -- never the block-upper tiles, which hold L_kk^-T after a backward solve.
+// ---------------------------------------------------------------------------
+constexpr int SWEEP_LDS = NTILES * TILE_BYTES + NT * 64 * 4 * 8;     // the staged block and the eight tiles of X_t
+
+__device__ __forceinline__ void load_xtile_rows(const double* p, int64_t ld, int lane, int rows, double (&x)[4]) {
+    x[0] = x[1] = x[2] = x[3] = 0.0;
+    if ((lane & 15) < rows) load_xtile(p, ld, lane, x);
+}
+__device__ __forceinline__ void store_xtile_rows(double* p, int64_t ld, int lane, int rows, const double (&x)[4]) {
+    if ((lane & 15) < rows) store_xtile(p, ld, lane, x);
+}
+// A-operand fragments of -M for the 16 x 16 tile M at `tile` in memory: what load_afrag reads from a published tile
+__device__ __forceinline__ void load_afrag_neg(const double* tile, int64_t ld, int lane, double (&a)[4]) {
+    const int i = lane & 15, kk = lane >> 4;
+    const int row = kap(i & 3, i >> 2);                     // rho(i)
+    const double* r = tile + (int64_t)row * ld + 2 * kk;
+    const d2 lo = *reinterpret_cast<const d2*>(r), hi = *reinterpret_cast<const d2*>(r + 8);
+    a[0] = -lo.x; a[1] = -lo.y; a[2] = -hi.x; a[3] = -hi.y;
+}
+
+__global__ __launch_bounds__(256) void border_sweep_kernel(const double* __restrict__ L, int64_t ldl, double* X, int64_t ldx,
+                                                           int rows, int64_t t) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    d2* tiles = reinterpret_cast<d2*>(smem);
+    double* xs = reinterpret_cast<double*>(smem + NTILES * TILE_BYTES);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t cb = t + blockIdx.x;                      // the column block of X (row block of L) of this workgroup
+    const bool solver = blockIdx.x == 0;
+    if (solver) stage_l_tiles<-1>(L + (int64_t)PB * t * (ldl + 1), ldl, tiles, lane, wave, nullptr);
+
+    double* Xc = X + (int64_t)PB * cb;
+    double acc[2][4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) load_xtile_rows(Xc + 16 * (wave + 4 * p), ldx, lane, rows, acc[p]);
+    if (t > 0) {
+        const double* Xk = X + (int64_t)PB * (t - 1);
+        double xk[NT][4];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) load_xtile_rows(Xk + 16 * j, ldx, lane, rows, xk[j]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const double* Lr = L + ((int64_t)PB * cb + 16 * (wave + 4 * p)) * ldl + (int64_t)PB * (t - 1);
+            double a[NT][4];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) load_afrag_neg(Lr + 16 * j, ldl, lane, a[j]);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tile_mma(a[j], xk[j], acc[p]);
+        }
+    }
+    if (!solver) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) store_xtile_rows(Xc + 16 * (wave + 4 * p), ldx, lane, rows, acc[p]);
+        return;
+    }
+    // workgroup 0: the updated block to wave 0 through LDS (lane-private slots), then trsm128's steps on it
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xs[((wave + 4 * p) * 64 + lane) * 4 + v] = acc[p][v];
+    __syncthreads();
+    if (wave != 0) return;
+    double xt[NT][4];
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xt[k][v] = xs[(k * 64 + lane) * 4 + v];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        double a[4], z[4] = {0., 0., 0., 0.};
+        load_afrag(tiles + trsm_slot<-1>(j, j) * 128, lane, a);
+        tile_mma(a, xt[j], z);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xt[j][v] = z[v];
+#pragma unroll
+        for (int k = j + 1; k < NT; ++k) {
+            double b[4];
+            load_afrag(tiles + trsm_slot<-1>(k, j) * 128, lane, b);
+            tile_mma(b, xt[j], xt[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int k = 0; k < NT; ++k) store_xtile_rows(Xc + 16 * k, ldx, lane, rows, xt[k]);
+}
+
 static hipError_t panel_mfma_attrs() {
     static PerDeviceOnce once;
     return once.run([]() -> hipError_t {
+        hipError_t es = hipFuncSetAttribute((const void*)border_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            SWEEP_LDS);
+        if (es != hipSuccess) return es;
         hipError_t e = hipFuncSetAttribute((const void*)trsm128_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            NTILES * TILE_BYTES);
         if (e != hipSuccess) return e;
@@ -599,6 +705,20 @@ hipError_t launch_trsm128(hipStream_t s, const double* L, int64_t ldl, double* X
     }
     hipLaunchKernelGGL(trsm128_kernel<-1>, dim3(grid), dim3(256), NTILES * TILE_BYTES, s, L, ldl, X, ldx, nslabs,
                        tuning().panel_stamps);
+    return hipGetLastError();
+}
+
+hipError_t launch_border_sweep(hipStream_t s, const double* L, int64_t ldl, int64_t ncols, double* X, int64_t ldx,
+                               int64_t rows) {
+    if (rows < 1 || rows > 16 || ncols < 0 || ncols % PB || ldl % 2 || ldx % 2 || ldl < ncols || ldx < ncols ||
+        (reinterpret_cast<uintptr_t>(L) & 15) || (reinterpret_cast<uintptr_t>(X) & 15))
+        return hipErrorInvalidValue;
+    if (ncols == 0) return hipSuccess;
+    hipError_t e = panel_mfma_attrs();
+    if (e != hipSuccess) return e;
+    const int64_t nblk = ncols / PB;
+    for (int64_t t = 0; t < nblk; ++t)
+        hipLaunchKernelGGL(border_sweep_kernel, dim3((unsigned)(nblk - t)), dim3(256), SWEEP_LDS, s, L, ldl, X, ldx, (int)rows, t);
     return hipGetLastError();
 }
 

@@ -268,6 +268,11 @@ class HipBlockOps:
         check(self.lib.gpmi_dev_trsm_block(self._stream(), self._p(L), self._ld(L), self._p(X), self._ld(X),
                                            X.shape[0], X.shape[1]))
 
+    def border_sweep(self, L, X, rows=None, ncols=None):
+        """X (rows <= 16) <- X L^-T for a fused factor L: the forward sweep behind GPContext.append for a few points"""
+        check(self.lib.gpmi_dev_border_sweep(self._stream(), self._p(L), self._ld(L), L.shape[0] if ncols is None else ncols,
+                                             self._p(X), self._ld(X), X.shape[0] if rows is None else rows))
+
     def gemm_nt(self, Cm, A, B):
         check(self.lib.gpmi_dev_gemm_nt(self._stream(), self._p(Cm), self._ld(Cm), self._p(A), self._ld(A),
                                         self._p(B), self._ld(B), Cm.shape[0], Cm.shape[1], A.shape[1], 0, 0))

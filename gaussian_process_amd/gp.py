@@ -247,6 +247,35 @@ class GPContext:
         self._set_train_ard(X, y, lengthscales)
         return self.factorize(sigma, l, noise_var)
 
+    def append(self, Xnew, ynew):
+        """k more observations into the resident regression fit in O(N^2 k): afterwards the context is what fit() on the
+        concatenated data with the same hyper-parameters would have left.  Returns the log-marginal-likelihood of the
+        N + k points; raises like factorize() when the extended matrix is not positive definite (the fit is then dropped,
+        the extended training set stays).  A single point may come as a 1-D row."""
+        Xnew = np.asarray(Xnew, dtype=np.float64)
+        if Xnew.ndim == 1:
+            Xnew = Xnew.reshape(1, -1)
+        Xnew = as_f64(Xnew, 2, "X_new")
+        ynew = as_f64(ynew, None, "y_new").reshape(-1)
+        if ynew.shape[0] != Xnew.shape[0]:
+            raise ValueError("X_new has %d rows but y_new has %d entries" % (Xnew.shape[0], ynew.shape[0]))
+        if self.d and Xnew.shape[1] != self.d:
+            raise ValueError("X_new has %d columns but the training set has %d" % (Xnew.shape[1], self.d))
+        lml = C.c_double()
+        bad = C.c_int64()
+        st = self._lib.gpmi_append(self._h, ptr(Xnew), Xnew.shape[0], ptr(ynew), C.byref(lml), C.byref(bad))
+        if st != _lib.GPMI_ERR_BAD_ARG:
+            self.N = self.layout()["N"]        # refused: nothing changed; otherwise the context says what is resident
+        check(st, bad.value)
+        return lml.value
+
+    def layout(self):
+        """{N, Np, ld, rows, route} of the resident training set and factor: whether an append stayed in place shows in
+        ld and rows; route is the last append's (1 skinny, 0 padded, -1 none yet)"""
+        out = (C.c_int64 * 5)()
+        check(self._lib.gpmi_get_layout(self._h, out))
+        return dict(zip(("N", "Np", "ld", "rows", "route"), (int(v) for v in out)))
+
     def alpha(self):
         out = np.empty(self.N)
         check(self._lib.gpmi_get_alpha(self._h, ptr(out)))

@@ -93,7 +93,10 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
  *               "trsv_vinv" (backward solve: 2 ONE launch, column blocks chained through the solution vector, with the
  *               inverted 128 x 128 diagonal blocks -- the default; 1 one launch per block with the same inverses; 0 the
  *               16 x 16 rounds),
- *               "trsm_wave" (0/1), "rbf_blocks" (persistent blocks of the K build).
+ *               "trsm_wave" (0/1), "rbf_blocks" (persistent blocks of the K build);
+ *               gpmi_append: "reserve" (default 0: from the next fit on A is sized for N + reserve points, so that appends
+ *               up to that size stay in place; setting it drops nothing), "append_skinny" (k <= 16 on a fused factor:
+ *               -1 by size -- the default --, 0 the padded 128-row sweep, 1 the <= 16-row sweep kernel whenever allowed).
  * The context-free gpmi_dev_* primitives run with the defaults. */
 int gpmi_set_option(gpmi_ctx* ctx, const char* name, int64_t value);
 
@@ -151,6 +154,32 @@ int gpmi_factorize(gpmi_ctx* ctx, double sigma, double ell, double noise_var,
 /* gpmi_set_train + gpmi_factorize in one call (host buffers in). */
 int gpmi_fit(gpmi_ctx* ctx, const double* X, int64_t N, int64_t d, const double* y,
              double sigma, double ell, double noise_var, double* lml, int64_t* bad_pivot);
+
+/* k more observations (Xnew: k x d, ynew: k) into the resident REGRESSION factorisation, in O(N^2 k): afterwards the
+ * context is what gpmi_fit on [X; Xnew], [y; ynew] with the resident kernel, lengthscales, sigma, ell and noise_var would
+ * have left -- N + k points, L, m = L^-1 y, and in *lml the LML of the N + k points -- to rounding (the factor's leading
+ * floor(N / 128) 128 rows are the resident ones bit for bit).  Every consumer of a regression fit works on it unchanged;
+ * v of a resident test set is dropped (gpmi_predict_resident recomputes it; gpmi_post_* ask for that first).
+ * With N0 = floor(N / 128) 128 only the border, rows [N0, ceil((N + k) / 128) 128), is built: its rows of K against the
+ * first N0 points swept through the resident factor (k <= 16 on a fused factor: the k new rows alone, by the kernel
+ * behind gpmi_dev_border_sweep; otherwise all border rows by the 128-row TRSM sweep; option "append_skinny"), one
+ * rank-N0 update of the border block and the y row, and the Cholesky of that block.  It works in place while the
+ * padded size fits the resident allocation (always inside the padding; beyond it with option "reserve"), and otherwise
+ * moves the leading N0 x N0 square into an allocation of the size a fresh fit would choose; if that allocation fails the
+ * call returns GPMI_ERR_RUNTIME with the old fit intact.  A runtime error behind the allocations (a copy, a launch)
+ * also returns GPMI_ERR_RUNTIME, but then as a failed pivot does: no fit resident, the training set the extended one
+ * (gpmi_get_layout tells N), gpmi_factorize works on it.
+ * Refused (GPMI_ERR_BAD_ARG, nothing changed): no regression factorisation resident ("no factorisation resident"),
+ * k < 1, NaN in Xnew or ynew, the composite kernel (kind 3).  Kinds 0, 1, 2, 4, 5, 6 and per-dimension lengthscales are
+ * supported.  A failed pivot of the border returns GPMI_ERR_NOT_PD with *bad_pivot its 1-based index among the N + k
+ * points and *lml NaN: the fit is dropped, the EXTENDED training set stays resident (gpmi_factorize works on it).
+ * Timers: GPMI_T_KS the row builds, GPMI_T_SOLVE_V the sweep, GPMI_T_CHOL the border update and factorisation,
+ * GPMI_T_LML.  lml / bad_pivot may be NULL. */
+int gpmi_append(gpmi_ctx* ctx, const double* Xnew, int64_t k, const double* ynew, double* lml, int64_t* bad_pivot);
+/* The layout of the resident training set and factor, for tests and the rate script: out5 = {N, Np (N padded to 128),
+ * the leading dimension of A, the rows A is laid out for, the route of the last gpmi_append that got as far as its sweep: 1 skinny,
+ * 0 padded, -1 none yet}.  The leading dimension and the rows are 0 until a fit has sized A. */
+int gpmi_get_layout(gpmi_ctx* ctx, int64_t* out5);
 
 /* alpha = solve(L.T, m)                               GP_regression.py:140
  * out: N doubles. */
@@ -515,6 +544,17 @@ int gpmi_dev_potrf_block(void* stream, double* A_dev, int64_t ld, int64_t nb,
  * leaves (option "trsm_wave"). */
 int gpmi_dev_trsm_block(void* stream, const double* L_dev, int64_t ldl, double* X_dev,
                         int64_t ldx, int64_t m, int64_t nb);
+/* X (rows x ncols, ldx) <- X * L^-T for 1 <= rows <= 16 and L the ncols x ncols lower factor (ldl) of a FUSED
+ * factorisation (ncols a multiple of 128, ldl and ldx even and >= ncols, both pointers 16-byte aligned): the forward
+ * sweep of gpmi_append for a few new points.  trsm128's recurrence on 16 x 16 tiles with the stored inverses; one launch
+ * per 128 columns, L streamed once, a fixed summation order (the same bits every run).  Measured it is bound by its
+ * chain of ncols / 128 dependent launches, not by memory: 0.35 of the streaming-read rate at ncols = 65536, 0.03 at 4096
+ * (profiles/r14_append_rate.txt).  Read of L: the
+ * tiles below the block diagonal, and of every 128 x 128 diagonal block its lower 16 x 16 tiles and its diagonal tiles
+ * whole -- never the block-upper tiles, which hold L_kk^-T after a backward solve.  Rows of X from `rows` on and columns
+ * from ncols on are neither read nor written; L is not written.  Anything else is refused with nothing launched. */
+int gpmi_dev_border_sweep(void* stream, const double* L_dev, int64_t ldl, int64_t ncols, double* X_dev, int64_t ldx,
+                          int64_t rows);
 /* C (M x N, ldc) -= A (M x K, lda) * B (N x K, ldb)^T.  lower != 0: only tiles
  * that intersect {col <= row + diag_off} are touched. */
 int gpmi_dev_gemm_nt(void* stream, double* C_dev, int64_t ldc, const double* A_dev, int64_t lda,
