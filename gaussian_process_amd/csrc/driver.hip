@@ -80,24 +80,18 @@ hipError_t trsm_block(hipStream_t s, const double* L, int64_t ldl, double* X, in
     return trsm_rec(s, L, ldl, X, ldx, m, 0, nb);
 }
 
-// Block widths of the sweep.  With a fixed width NB the first panel (NB columns x all rows) runs
-// before there is any trailing update to hide it behind, and the last few panels are longer than
-// the updates they overlap.  Option "ramp" lets the widths ramp up (NB/4, NB/4, NB/2, then NB)
-// and down again over the last columns.  Measured at N = 65536: the exposed panel time drops by
-// 7 ms but the narrower first updates cost 14 ms, so it is off by default.
-std::vector<int64_t> block_schedule(const gpmi_ctx* c, int64_t ncols) {
-    return plan_block_widths(c->block(ncols), ncols, c->nb == 0, c->ramp);      // gpmi_plan.h
-}
-
 // In-place blocked right-looking Cholesky of the leading ncols x ncols block of
 // A; rows ncols..nrows-1 are carried along (they end up multiplied by L^-T).
+// Without lookahead every step is a panel and one trailing update on the main stream.
 //
 // With lookahead the trailing update of step k is split in two launches: (a) the next
 // block column only and (b) the rest.  (a) goes on the panel stream (high priority), right behind panel k and in
 // front of panel k+1, (b) on the main stream.  (a) and (b) write different columns
 // and both only read panel k, so they start together: the tail of (a) -- a launch whose last
-// tiles leave most CUs idle -- and the whole latency-bound panel k+1 run under (b).
-// (Option "slack_forms" without bit 1: from 49152 columns up (a) then (b) on the main stream, panel k+1 behind (a).)
+// tiles leave most CUs idle -- and the whole latency-bound panel k+1 run under (b).  That pays at mid sizes
+// (N = 16384: -4 %, 32768: -1 %), where a launch's tail and the panel chain are a visible share of a step, and at
+// the headline size, where the tail of (a) is a smaller share but a 256 x 128 one, twice as long as a 128 x 128 tail
+// (LAB_NOTES.md, "leftover 128 x 128 updates").
 // From 49152 columns up the panel chain is 4-5x shorter than the step it runs under, so nothing on the critical path
 // waits for a workgroup that holds its CU twice as long: the launches of such a factorisation -- (a), (b) and the
 // updates inside the panel -- take the 256 x 128 form from tall_min_tiles_slack live tiles on (Sharing::panel_slack).
@@ -108,26 +102,17 @@ std::vector<int64_t> block_schedule(const gpmi_ctx* c, int64_t ncols) {
 //   (b)_k    ->  (a)_{k+1}             (panel stream waits on the event behind (b)_k)
 //   (b)_k    ->  (b)_{k+1}             (same stream)
 hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, int64_t nrows,
-                            int64_t* info, bool account, int64_t carried_rows, const SweepFollower* follow) {
+                            int64_t* info, bool account, int64_t carried_rows) {
     hipError_t e;
     hipStream_t sm = c->stream;
-    const std::vector<int64_t> widths = block_schedule(c, ncols);
     const int64_t NB = c->block(ncols);
-    // below ~12k columns the two-stream choreography costs more than the panel it hides
-    const bool la = c->lookahead && c->pstream && ncols > NB && ncols >= c->la_min;
+    const bool la = c->lookahead_for(ncols);
     hipStream_t sp_ = la ? c->pstream : sm;
     // panel kernels beside the trailing update use their small-LDS forms -- while there IS a trailing update of some length
     // to run beside: once the columns right of the panel are fewer than c->shallow_min, part (b) of a step is over long
     // before the panel chain is, and the one-launch forms (which then find empty CUs) are the shorter chain
-    const bool large = la && ncols >= 49152;
-    const bool slack = large && (c->slack_forms & 1);
-    SharingScope shallow((la || follow) ? Sharing::beside_update().with_panel_slack(slack) : sharing());
-    // (a) on the panel stream pays at mid sizes (N = 16384: -4 %, 32768: -1 %), where a launch's tail and the
-    // panel chain are a visible share of a step.  At the headline size the tail of (a) is a smaller share, but a
-    // 256 x 128 tail is twice as long as the 128 x 128 one: (a) runs beside (b) there as well (the numbers:
-    // LAB_NOTES.md, "leftover 128 x 128 updates").  (a) is then timed with the panel and launched under the generic
-    // symbol at every size: "time per launch" (the roofline figure) covers the (b) launches only
-    const bool col_on_panel = la && (!large || (c->slack_forms & 2));
+    const bool slack = la && ncols >= 49152;
+    SharingScope shallow(la ? Sharing::beside_update().with_panel_slack(slack) : sharing());
     const int slot_p = account ? GPMI_T_CHOL_PANEL : GPMI_T_COUNT - 1;
     const int slot_t = account ? GPMI_T_CHOL_TRAIL : GPMI_T_COUNT - 1;
     if (la && (e = c->order(sm, sp_)) != hipSuccess) return e;   // panel 0 after the K build
@@ -154,10 +139,9 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         }
         return er;
     };
-    int64_t k = 0;
     hipEvent_t ev_b = nullptr;                    // behind the last (b) on the main stream
-    for (size_t step = 0; step < widths.size(); ++step) {
-        const int64_t nb = widths[step];
+    for (int64_t k = 0; k < ncols; k += NB) {
+        const int64_t nb = std::min<int64_t>(NB, ncols - k);
         size_t sp = c->span_begin(slot_p, sp_);
         {
             SharingScope panel_forms(!la ? sharing().large_lds()
@@ -168,43 +152,17 @@ hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, i
         if (e != hipSuccess) return e;
         if (la && (e = c->order(sp_, sm)) != hipSuccess) return e;
         const int64_t r0 = k + nb;
-        if (follow) {
-            // block column k of L is final: the following rows' solve against L_kk and their update by it, behind their own
-            // step k-1 on their stream -- nothing of the factorisation waits for them
-            if ((e = c->order(sp_, follow->vs)) != hipSuccess) return e;
-            {
-                // as in solve_sweep: the small-LDS solve forms only for enough rows to matter beside the updates
-                SharingScope solve_forms(follow->m >= 2048 ? Sharing::beside_update() : Sharing::chip_shared_only());
-                if ((e = trsm_block(follow->vs, A + k * ld + k, ld, follow->V + k, follow->ldv, follow->m, nb)) != hipSuccess) return e;
-            }
-            if (r0 < ncols) {
-                // V[:, r0..) -= V[:, k..k+nb) * L[r0.., k..k+nb)^T
-                const GemmArgs g = gemm_minus(follow->V + r0, follow->ldv, follow->V + k, follow->ldv, A + r0 * ld + k, ld,
-                                              follow->m, ncols - r0, nb);
-                SharingScope update_forms(sharing().with_panel_slack(false));       // the following rows keep their forms
-                if ((e = launch_gemm_nt(follow->vs, g)) != hipSuccess) return e;
-            }
-        }
-        k = r0;
         if (r0 >= ncols) continue;
         if (!la) {
-            if ((e = trail(sm, true, r0, r0, r0 - nb, nb, ncols - r0)) != hipSuccess) return e;
+            if ((e = trail(sm, true, r0, r0, k, nb, ncols - r0)) != hipSuccess) return e;
             continue;
         }
-        const int64_t nbn = widths[step + 1];
-        if (!col_on_panel) {
-            // (a) then (b) on the main stream, panel k+1 behind (a)
-            if ((e = trail(sm, true, r0, r0, r0 - nb, nb, nbn)) != hipSuccess) return e;
-            if ((e = c->order(sm, sp_)) != hipSuccess) return e;
-            if (r0 + nbn < ncols &&
-                (e = trail(sm, true, r0 + nbn, r0 + nbn, r0 - nb, nb, ncols - r0 - nbn)) != hipSuccess) return e;
-            continue;
-        }
+        const int64_t nbn = std::min<int64_t>(NB, ncols - r0);
         // (a) next block column, behind panel k on the panel stream and behind (b) of the step before
         if (ev_b && (e = hipStreamWaitEvent(sp_, ev_b, 0)) != hipSuccess) return e;
-        if ((e = trail(sp_, false, r0, r0, r0 - nb, nb, nbn)) != hipSuccess) return e;
+        if ((e = trail(sp_, false, r0, r0, k, nb, nbn)) != hipSuccess) return e;
         if (r0 + nbn < ncols) {                                                          // (b) rest
-            if ((e = trail(sm, true, r0 + nbn, r0 + nbn, r0 - nb, nb, ncols - r0 - nbn)) != hipSuccess) return e;
+            if ((e = trail(sm, true, r0 + nbn, r0 + nbn, k, nb, ncols - r0 - nbn)) != hipSuccess) return e;
             ev_b = c->new_event();
             if (!ev_b) return c->ev_error;
             if ((e = hipEventRecord(ev_b, sm)) != hipSuccess) return e;
@@ -288,24 +246,14 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     if (c->kind == 2 && c->d != 1) return fail_arg("gpmi_factorize: the periodic kernel is 1-D only (GP_regression.py:48)");
     if (!cov_stationary(c->kind) && c->ard())
         return fail_arg("gpmi_factorize: per-dimension lengthscales need the squared-exponential or a Matern kernel (kinds 0, 4, 5, 6)");
-    // the test set's rows: inside the panel and update launches (1) or one block column behind on their own stream (2)
-    int form = 0;
-    if (with_test) {
-        // measured (profiles/r04_one_pass_ab.txt, ms for two calls / ride / follow): N = 2048 1.69 / 1.32 / 1.49, 8192 10.5 / 8.94 /
-        // 8.74, 16384 37.5 / 34.9 / 34.9, 32768 262.7 / 257.9 / 256.7, 65536 1702 / 1698 / 1710 -- the chip is work-conserving
-        // either way, and riding costs no launches: the default at every size
-        form = c->one_pass_form ? c->one_pass_form : 1;
-        if (with_post) form = 3;                   // the augmented matrix: the rows ride (there is no other way) with columns of their own
-        if (form == 2 && !c->vstream) {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            HIP_TRY(hipStreamCreateWithPriority(&c->vstream, hipStreamNonBlocking, lo));
-        }
-    }
+    // with_test: the test set's rows ride inside the panel and update launches of the factorisation (against a solve call
+    // of their own, profiles/r04_one_pass_ab.txt, ms: N = 2048 1.69 -> 1.32, 8192 10.5 -> 8.94, 16384 37.5 -> 34.9, 32768
+    // 262.7 -> 257.9, 65536 1702 -> 1698: riding costs no launches).  with_post (only with with_test): the augmented matrix,
+    // where they ride with columns of their own
     if (with_post && std::isnan(jitter)) return fail_arg("gpmi_fit_predict_sample: jitter is NaN");
     c->res.drop_fit();                // a regression factorisation replaces whatever fit was resident
     c->release_sparse_grad();
-    int rc = ensure_train_buffers(c, with_test ? c->np_ : 0, form == 3);
+    int rc = ensure_train_buffers(c, with_test ? c->np_ : 0, with_post);
     if (rc) return rc;
     hipStream_t s = c->stream;
     c->timers_reset({GPMI_T_KBUILD, GPMI_T_CHOL, GPMI_T_CHOL_PANEL, GPMI_T_CHOL_TRAIL, GPMI_T_LML,
@@ -323,16 +271,16 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     HIP_TRY(launch_rbf(s, r));
     c->span_end(sp);                  // GPMI_T_KBUILD is the kernel-matrix build (a1 + a2) alone
     // the augmented rows: y then zeros (a4 rides in the factorisation)
-    const int64_t ncols = c->Np + (form == 3 ? c->np_ : 0);   // columns of the factorisation
+    const int64_t ncols = c->Np + (with_post ? c->np_ : 0);   // columns of the factorisation
     HIP_TRY(launch_fill_rows(s, c->m_row(), c->ldA, TILE, ncols, 0.0));
     HIP_TRY(launch_set_yrow(s, c->m_row(), c->y.as<double>(), c->N, c->Np));
-    c->v_row0 = form == 3 ? c->Np : c->Np + TILE;
+    c->v_row0 = with_post ? c->Np : c->Np + TILE;
     double* Vr = A + c->v_row0 * c->ldA;
     if (with_test) {                  // K(X*, X) below the y rows (a1 for K_s, GP_regression.py:127): they leave as v^T
         sp = c->span_begin(GPMI_T_KS);
         const RbfArgs t = rbf_test_train(c, Vr, c->ldA);
         HIP_TRY(launch_rbf(s, t));
-        if (form == 3) {              // K_ss + jitter I in the rows' own columns, lower tiles (GP_regression.py:128, 154)
+        if (with_post) {              // K_ss + jitter I in the rows' own columns, lower tiles (GP_regression.py:128, 154)
             const RbfArgs q = rbf_sym(c, c->x_test(), c->n, c->box_test(), jitter, c->np_, Vr + c->Np, c->ldA);
             HIP_TRY(launch_rbf(s, q));
         }
@@ -340,19 +288,8 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     }
 
     sp = c->span_begin(GPMI_T_CHOL);
-    if (form == 2) {
-        SweepFollower f;
-        f.V = Vr; f.ldv = c->ldA; f.m = c->np_; f.vs = c->vstream;
-        HIP_TRY(c->order(s, f.vs));                     // K(X*, X) is in place
-        size_t spv = c->span_begin(GPMI_T_SOLVE_V, f.vs);
-        HIP_TRY(cholesky_inplace(c, A, c->ldA, c->Np, c->Np + TILE, c->info.as<int64_t>(), true, 0, &f));
-        c->span_end(spv, f.vs);
-        HIP_TRY(c->order(f.vs, s));
-    } else if (form == 3) {
-        HIP_TRY(cholesky_inplace(c, A, c->ldA, ncols, c->Mp, c->info.as<int64_t>(), true, 0));
-    } else {
-        HIP_TRY(cholesky_inplace(c, A, c->ldA, c->Np, c->Mp, c->info.as<int64_t>(), true, with_test ? c->n : 0));
-    }
+    // test rows with columns of their own are rows of the factorisation, not carried ones
+    HIP_TRY(cholesky_inplace(c, A, c->ldA, ncols, c->Mp, c->info.as<int64_t>(), true, with_test && !with_post ? c->n : 0));
     c->span_end(sp);
 
     sp = c->span_begin(GPMI_T_LML);
@@ -375,7 +312,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     HIP_TRY(hipMemcpyAsync(&info, c->info.p, sizeof info, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
-    if (info != big && (info < c->N || (form == 3 && info >= c->Np && info < c->Np + c->n))) {
+    if (info != big && (info < c->N || (with_post && info >= c->Np && info < c->Np + c->n))) {
         // a pivot of K + sI (GP_regression.py:138) or, in the augmented form, of the posterior covariance (:154; counted from
         // its own first column, as gpmi_post_chol reports it)
         if (bad_pivot) *bad_pivot = info < c->N ? info + 1 : info - c->Np + 1;
@@ -390,7 +327,7 @@ int factorize_impl(gpmi_ctx* c, double sigma, double ell, double noise_var, doub
     c->res.fit_done(Fit::Regression);
     if (with_test) {
         c->ldV = c->ldA;
-        c->res.v_in_rows_of_A(form == 3, jitter);
+        c->res.v_in_rows_of_A(with_post, jitter);
         meanvar_to_host(c, h, mu, out2, want_sd);
     }
     return GPMI_OK;
@@ -410,7 +347,7 @@ hipError_t solve_sweep_factor(gpmi_ctx* c, const double* A, int64_t ld, int64_t 
     hipError_t e;
     hipStream_t sm = c->stream;
     const int64_t NB = c->block(Np);
-    const bool la = c->lookahead && c->pstream && Np > NB && Np >= c->la_min;
+    const bool la = c->lookahead_for(Np);
     hipStream_t sp_ = la ? c->pstream : sm;
     // small-LDS panel forms beside the update only for sweeps with enough rows to keep the chip busy: for a few
     // hundred test points the chain of launches is what counts, and the one-launch trsm128 is shorter

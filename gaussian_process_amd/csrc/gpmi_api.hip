@@ -84,7 +84,6 @@ int gpmi_ctx_create(int device, gpmi_ctx** out) {
     if ((env = getenv("GPMI_NB"))) c->nb = std::max<int64_t>(128, atoll(env) / 128 * 128);
     if ((env = getenv("GPMI_LD_PAD"))) c->ld_pad = std::max<int64_t>(0, atoll(env) / 2 * 2);
     if ((env = getenv("GPMI_LOOKAHEAD"))) c->lookahead = atoi(env) ? 1 : 0;
-    if ((env = getenv("GPMI_SLACK_FORMS"))) c->slack_forms = atoi(env) & 3;
     *out = c;
     return GPMI_OK;
 }
@@ -104,7 +103,6 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
     (void)hipStreamDestroy(c->pstream);
-    if (c->vstream) (void)hipStreamDestroy(c->vstream);
     delete c;
     return GPMI_OK;
 }
@@ -171,12 +169,6 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "shallow_min")) {
         if (value < 0) return fail_arg("shallow_min must be >= 0");
         c->shallow_min = value;
-    } else if (!strcmp(name, "slack_forms")) {
-        if (value < 0 || value > 3) return fail_arg("slack_forms: bit 0 the lower bar of the 256 x 128 form, bit 1 the next block column on the panel stream");
-        c->slack_forms = (int)value;
-    } else if (!strcmp(name, "one_pass_form")) {
-        if (value < 0 || value > 2) return fail_arg("one_pass_form must be 0 (by size), 1 (rows ride) or 2 (rows follow)");
-        c->one_pass_form = (int)value;
     } else if (!strcmp(name, "sparse_slab")) {
         if (value < 0) return fail_arg("sparse_slab must be >= 0 (0: by size)");
         c->sparse_slab = value;
@@ -190,11 +182,6 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "lanes")) {
         if (value < 0 || value > 8) return fail_arg("lanes must be 0 (by size) .. 8");
         c->lanes = (int)value;
-    } else if (!strcmp(name, "ramp")) {
-        // bit mask: 1 ramp up, 2 half width over the last blocks, 4 quarter width for the last block, bits 4.. = how many
-        // blocks count as "last" (0: three)
-        if (value < 0 || (value & 8) || (value >> 4) > 64) return fail_arg("ramp: bits 0-2 and a tail count of at most 64 in bits 4..");
-        c->ramp = (int)value;
     } else {
         const int rc = set_tuning_option(c->tune, name, value);
         if (rc < 0) return fail_arg("gpmi_set_option: unknown option");
@@ -573,7 +560,7 @@ int gpmi_post_sample(gpmi_ctx* c, double jitter, const double* Z, int64_t num_fu
 // 0.45 -> 0.24 ms, N = 2048 1.74 -> 0.93 ms, N = 8192 10.5 -> 6.9 ms, N = 16384 39.5 -> 32.1 ms,
 // N = 32768 213 -> 201 ms).
 static int lane_prepare(gpmi_ctx* c, gpmi_ctx* l) {
-    l->nb = c->nb; l->ld_pad = c->ld_pad; l->lookahead = c->lookahead; l->la_min = c->la_min; l->ramp = c->ramp; l->timing = c->timing;
+    l->nb = c->nb; l->ld_pad = c->ld_pad; l->lookahead = c->lookahead; l->la_min = c->la_min; l->timing = c->timing;
     l->tune = c->tune;
     l->kind = c->kind; l->kp0 = c->kp0; l->kp1 = c->kp1;
     for (int i = 0; i < 11; ++i) l->kpv[i] = c->kpv[i];

@@ -126,7 +126,6 @@ struct gpmi_ctx {
     int device = 0;
     hipStream_t stream = nullptr;    // main stream: K build, trailing updates, reductions
     hipStream_t pstream = nullptr;   // high-priority stream: panel factorisations (lookahead)
-    hipStream_t vstream = nullptr;   // one-pass prediction, form "follow": the test set's sweep, one block column behind the Cholesky
     // options
     int64_t nb = 0;         // outer block width of the Cholesky (multiple of 128); 0 = by size
     int64_t block(int64_t ncols) const { return nb ? nb : (ncols >= 32768 ? 2048 : ncols >= 12288 ? 1024 : 512); }
@@ -137,14 +136,10 @@ struct gpmi_ctx {
                             // profiles/r04_la_min_sweep.txt -- one pass / two calls / fit alone at N = 4096: 3.06 -> 2.96 / 3.82 -> 3.86 /
                             // 2.56 -> 2.59 ms, 6144: 5.41 -> 5.20 / 6.69 -> 6.50 / 4.67 -> 4.48, 10240: 13.8 -> 12.6 / 15.9 -> 14.7; same bits)
     int64_t shallow_min = 6144; // under lookahead, panels with fewer columns left than this use the one-launch panel kernels (0: never)
-    int slack_forms = 3;    // Cholesky of 49152 columns and more (the panel chain has slack), bit mask: 1 the 256 x 128 update form from
-                            // tall_min_tiles_slack live tiles on (Sharing::panel_slack), 2 part (a) of a step on the panel stream as below 49152
-    int one_pass_form = 0;  // gpmi_fit_predict_resident: 1 the test set's rows ride in the panel and update launches, 2 they follow on a
-                            // stream of their own (panel k done -> their solve against L_kk -> their update), 0 = by size
+    // the blocked sweeps (cholesky_inplace, solve_sweep_factor) run their panel chain on pstream beside the update
+    bool lookahead_for(int64_t ncols) const { return lookahead && pstream && ncols > block(ncols) && ncols >= la_min; }
     int lanes = 0;          // gpmi_lml_batch: factorisations in flight (0 = by size)
     std::vector<gpmi_ctx*> lane_ctx;   // the extra lanes (own streams and workspaces), created on demand
-    int ramp = 0;           // block-width schedule, bit mask: 1 ramp up at the start, 2 half width over the last blocks (count in bits 4.., default 3),
-                            // 4 quarter width for the last block (measured: ramp up 0.4 % slower at N = 65536; ramp down within noise at N = 16384 / 32768: off)
     int64_t reserve = 0;    // ensure_train_buffers sizes A for N + reserve points, so that gpmi_append stays in place
     int append_route = -1;  // the route the last gpmi_append took: 1 skinny, 0 padded (gpmi_get_layout)
     int append_skinny = -1; // gpmi_append, k <= 16 on a fused factor: -1 by size, 0 the padded 128-row sweep, 1 the <= 16-row kernel
@@ -275,14 +270,8 @@ namespace gpmi {
 hipError_t panel_factor(hipStream_t s, double* A, int64_t ld, int64_t nb, int64_t mrows, int64_t col_offset,
                         int64_t* info);
 hipError_t trsm_block(hipStream_t s, const double* L, int64_t ldl, double* X, int64_t ldx, int64_t m, int64_t nb);
-// rows that follow the factorisation on a stream of their own: V (m x ncols, leading dimension ldv) <- V L^-T
-struct SweepFollower {
-    double* V = nullptr;
-    int64_t ldv = 0, m = 0;
-    hipStream_t vs = nullptr;
-};
 hipError_t cholesky_inplace(gpmi_ctx* c, double* A, int64_t ld, int64_t ncols, int64_t nrows, int64_t* info,
-                            bool account, int64_t carried_rows = 0, const SweepFollower* follow = nullptr);
+                            bool account, int64_t carried_rows = 0);
 hipError_t solve_sweep(gpmi_ctx* c, double* V, int64_t ldv, int64_t m, bool tri = false);
 // the same sweep through any resident lower factor (ncols x ncols, leading dimension ld), not only the one in c->A
 hipError_t solve_sweep_factor(gpmi_ctx* c, const double* L, int64_t ld, int64_t ncols, double* V, int64_t ldv, int64_t m,

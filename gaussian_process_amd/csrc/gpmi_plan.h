@@ -1,6 +1,6 @@
 // Host-side planning of the launches, free of any HIP dependency: which tiles a GEMM launch enumerates and in what
-// order (XCD-aware supertiles, the triangular and the staircase enumerations), which of them are live, how the block
-// widths of a blocked sweep are laid out, and the algorithmic flop counts the bench line is priced on.
+// order (XCD-aware supertiles, the triangular and the staircase enumerations), which of them are live, and the
+// algorithmic flop counts the bench line is priced on.
 // The same header is compiled by hipcc into the kernels (block -> tile map) and by plain g++ under
 // -fsanitize=address,undefined in tests/test_sanitize_cpu.py, where tests/sanitize/plan_check.cpp holds every plan
 // against brute force (each live tile enumerated exactly once, no dead one, no table overrun).
@@ -9,7 +9,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <vector>
 
 #if defined(__HIPCC__)
 #define GPMI_HD __host__ __device__ __forceinline__
@@ -280,30 +279,6 @@ inline int64_t plan_live_tiles(int64_t Tm, int64_t Tn, int lower, int64_t diag_o
         n += w;
     }
     return n;
-}
-
-// Block widths of a blocked sweep over ncols columns at nominal width NB.  ramp (bit mask, only with ramp_ok): 1 ramp up
-// at the start (NB/4, NB/4, NB/2), 2 half width over the last `ramp >> 4` (default 3) blocks, 4 quarter width for the
-// last block.
-inline std::vector<int64_t> plan_block_widths(int64_t NB, int64_t ncols, bool ramp_ok, int ramp) {
-    std::vector<int64_t> w;
-    if (NB <= 0 || ncols <= 0) return w;
-    const bool on = ramp_ok && ramp && NB >= 1024 && ncols >= 8 * NB;
-    const bool up = on && (ramp & 1), down = on && (ramp & 2);
-    const int64_t tail = (ramp >> 4) ? (ramp >> 4) : 3;       // blocks at the end that run at half width
-    int64_t done = 0;
-    while (done < ncols) {
-        int64_t nb = NB;
-        const int64_t left = ncols - done;
-        if (up && w.size() < 2) nb = NB / 4;
-        else if (up && w.size() < 3) nb = NB / 2;
-        else if (down && left <= NB && (ramp & 4)) nb = NB / 4;
-        else if (down && left <= tail * NB) nb = NB / 2;
-        nb = std::min(nb, ncols - done);
-        w.push_back(nb);
-        done += nb;
-    }
-    return w;
 }
 
 // flops the tiles of a launch compute (whole tiles; TN = 128 when N % 128 == 0, else 64)

@@ -70,26 +70,18 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
 /* tuning knobs; unknown names -> GPMI_ERR_BAD_ARG.
  * per context:  "nb" (outer Cholesky block, 0 = by size), "ld_pad" (doubles added to leading dimensions),
  *               "timing" (0/1: hipEvent stage timers), "lookahead" (0/1), "la_min" (columns from which lookahead is used,
- *               default 12288), "one_pass_form" (gpmi_fit_predict_resident: 0 by size, 1 the test rows ride inside the
- *               panel and update launches, 2 they follow on a stream of their own), "lanes" (factorisations in flight in
- *               gpmi_lml_batch, 0 = by size), "ramp" (bit mask, default 0: 1 block widths ramp up at the start of the
- *               sweep, 2 half width over the last blocks, 4 quarter width for the last one, bits 4.. = how many blocks
- *               count as "last" (0: three), when "nb" is automatic.  Until round 2 any non-zero value meant "up and
- *               down": that is 3 now; other bits or a negative value are refused),
+ *               default 12288), "lanes" (factorisations in flight in gpmi_lml_batch, 0 = by size),
  *               "sparse_slab" (gpmi_sparse_fit: training rows per slab, rounded up to 128; 0 = by size (16384).  It bounds
  *               the slab workspace to that many rows of m + "ld_pad" doubles whatever N is; same results to rounding),
  *               "shallow_min" (under lookahead, panels with fewer columns left than this use the one-launch panel
- *               kernels: the update they would run beside is over long before they are; default 6144, 0 = never),
- *               "slack_forms" (a Cholesky of 49152 columns and more, whose lookahead panel chain is far off the critical
- *               path; bit mask, default 3: 1 its update launches take the 256 x 128 form from "tall_min_tiles_slack" live
- *               tiles on instead of "tall_min_tiles", 2 the update of the next block column runs on the panel stream
- *               beside the rest of the step, as it does below 49152 columns; same results whatever the value);
+ *               kernels: the update they would run beside is over long before they are; default 6144, 0 = never);
  *               kernel selection (for measurements; also per context -- the lanes of gpmi_lml_batch inherit them):
  *               "panel_fused" (0/1: 128-column MFMA panel kernels / first-generation 64-column leaves),
  *               "gemm_dma" (0/1), "gemm_dma_waves" (4/8), "gemm_small_tiles" (0/1), "gemm_small_dma" (0/1),
  *               "gemm_persist" (0/1: resident workgroups for update GEMMs that have the chip to themselves),
  *               "gemm_tall" (0/1: 256 x 128 blocks for per-tile update launches of at least "tall_min_tiles" live
- *               128 x 128 tiles, default 12288 -- "tall_min_tiles_slack", default 1024, under "slack_forms" bit 0),
+ *               128 x 128 tiles, default 12288 -- "tall_min_tiles_slack", default 1024, in a Cholesky of 49152 columns
+ *               and more under lookahead, whose panel chain is far off the critical path),
  *               "trsv_vinv" (backward solve: 2 ONE launch, column blocks chained through the solution vector, with the
  *               inverted 128 x 128 diagonal blocks -- the default; 1 one launch per block with the same inverses; 0 the
  *               16 x 16 rounds),

@@ -1,4 +1,4 @@
-"""prediction() in one pass (+ alpha) against context options that were tuned on the two-call form: shallow_min, ramp.
+"""prediction() in one pass (+ alpha) against a context option that was tuned on the two-call form: shallow_min.
    python scripts/one_pass_opts.py N n"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +11,7 @@ X, y, Xs = O.synthetic_problem(N, 8, n)
 ctx = GPContext(0)
 ctx.set_train(X, y); ctx.set_test(Xs)
 ref = None
-for name, vals, default in (("shallow_min", (6144, 0, 2048, 4096, 8192, 12288), 6144), ("ramp", (0, 2, 2 + 16 * 2, 2 + 16 * 4, 6), 0)):
+for name, vals, default in (("shallow_min", (6144, 0, 2048, 4096, 8192, 12288), 6144),):
     for v in vals:
         ctx.set_option(name, v)
         ts = []

@@ -2,7 +2,7 @@
 calls, total ms, and -- for the update-GEMM symbols -- the algorithmic flops each carried, split by the role of the
 launch: (a) next block column, (b) rest of the trailing update, panel-internal update (panel_rec).
 
-    python scripts/update_symbol_table.py TRACE_kernel_trace.csv [--size 65536 --ntest 4096 --slack-forms 3]
+    python scripts/update_symbol_table.py TRACE_kernel_trace.csv [--size 65536 --ntest 4096]
 
 The trace does not carry K or the role, so the launches of the factorisation are restated here (cholesky_inplace,
 panel_rec and gemm_route for the default options: block 2048 from 32768 columns, lookahead, 128-column leaves) and laid
@@ -27,12 +27,10 @@ def flops(M, N, K, real_rows):
     return 2.0 * K * (tri * (tri + 1) / 2.0 + max(0, rows - tri) * N)
 
 
-def launches(ncols, nrows, carried, slack_forms, tall_min=12288, tall_min_slack=1024):
+def launches(ncols, nrows, carried, tall_min=12288, tall_min_slack=1024):
     """(symbol, role, flops) of every LDS-DMA-family update launch of one factorisation, per stream in issue order"""
     nb = 2048 if ncols >= 32768 else 1024 if ncols >= 12288 else 512
-    large = ncols >= 49152
-    bar = tall_min_slack if large and slack_forms & 1 else tall_min
-    a_on_panel = not large or slack_forms & 2
+    bar = tall_min_slack if ncols >= 49152 else tall_min
     out = []
 
     def gemm(role, counted, r0, M, N, K):
@@ -56,7 +54,7 @@ def launches(ncols, nrows, carried, slack_forms, tall_min=12288, tall_min_slack=
         r0 = k + nb
         if r0 >= ncols:
             break
-        gemm("(a)", not a_on_panel, r0, nrows - r0, nb, nb)
+        gemm("(a)", False, r0, nrows - r0, nb, nb)
         if r0 + nb < ncols:
             gemm("(b)", True, r0 + nb, nrows - r0 - nb, ncols - r0 - nb, nb)
     return out
@@ -67,7 +65,6 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--size", type=int, default=65536)
     ap.add_argument("--ntest", type=int, default=4096)
-    ap.add_argument("--slack-forms", type=int, default=3, help="option slack_forms of the traced build (the parent of it: 0)")
     args = ap.parse_args()
     rows = list(csv.DictReader(open(args.trace)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -76,7 +73,7 @@ def main():
         name = r["Kernel_Name"].replace("void ", "").replace("gpmi::", "").split("(")[0]
         by_sym.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6)
     ncols = (args.size + 127) // 128 * 128
-    model = launches(ncols, ncols + 128 + args.ntest, args.ntest, args.slack_forms)
+    model = launches(ncols, ncols + 128 + args.ntest, args.ntest)
     per_sym = collections.defaultdict(list)
     for sym, role, f in model:
         per_sym[sym].append((role, f))

@@ -3,7 +3,7 @@
 //   * every plan enumerates each live tile exactly once and no dead one (rectangles, lower triangles with any diagonal
 //     offset, row maps with and without a host copy, ragged Tm / Tn, every supertile edge, M up to 131072);
 //   * a staircase with more supertile rows than the table holds falls back to the rectangle -- it never overruns;
-//   * block-width schedules cover the columns exactly; the flop counts agree with element-by-element sums.
+//   * the flop counts agree with element-by-element sums.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -152,17 +152,6 @@ int main() {
     // refused arguments
     { TilePlan p; CHECK(!plan_tiles(p, 0, 4, 0, 0, false, nullptr, 0, 1), "Tm = 0 accepted");
       int32_t one = 128; CHECK(!plan_tiles(p, 4, 4, 0, 0, true, &one, 0, 1), "row_bands = 0 accepted"); }
-    // block-width schedules
-    for (int64_t NB : {(int64_t)128, (int64_t)512, (int64_t)1024, (int64_t)2048})
-        for (int64_t ncols : {(int64_t)128, (int64_t)1024, (int64_t)12288, (int64_t)16384, (int64_t)65536, (int64_t)131072, (int64_t)65536 + 128})
-            for (int ramp : {0, 1, 2, 3, 7, 2 | (5 << 4)}) {
-                const std::vector<int64_t> w = plan_block_widths(NB, ncols, true, ramp);
-                int64_t sum = 0;
-                for (int64_t v : w) { CHECK(v > 0 && v <= NB, "width %ld", (long)v); sum += v; }
-                CHECK(sum == ncols, "widths sum %ld != %ld", (long)sum, (long)ncols);
-                const std::vector<int64_t> w0 = plan_block_widths(NB, ncols, false, ramp);
-                for (size_t i = 0; i + 1 < w0.size(); ++i) CHECK(w0[i] == NB, "fixed schedule");
-            }
     // flop counts against element-by-element sums
     for (int trial = 0; trial < 200; ++trial) {
         const int64_t M = 128 * (1 + rng() % 12), N = 128 * (1 + rng() % 12), K = 16 * (1 + rng() % 8);

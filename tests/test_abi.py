@@ -56,6 +56,19 @@ def test_retired_resident_experiment_options_and_probes_are_gone():
         assert not hasattr(raw, name), name
 
 
+@pytest.mark.gpu
+def test_retired_sweep_schedule_options_are_gone(ctx):
+    """block widths that grow and shrink along the sweep, the test rows on a stream of their own behind the factorisation
+    and the switches of the schedule from 49152 columns up were removed with the schedules they selected: their option
+    names are unknown to a context, the thresholds of the one schedule there is still take their defaults"""
+    from gaussian_process_amd import _lib
+    for name in (b"ramp", b"one_pass_form", b"slack_forms"):
+        assert ctx._lib.gpmi_set_option(ctx._h, name, 0) == _lib.GPMI_ERR_BAD_ARG, name
+        assert "unknown option" in _lib.last_error(), name
+    for name, default in ((b"la_min", 6144), (b"shallow_min", 6144), (b"lookahead", 1), (b"nb", 0)):
+        assert ctx._lib.gpmi_set_option(ctx._h, name, default) == _lib.GPMI_OK, _lib.last_error()
+
+
 def test_no_silent_cpu_fallback_without_gpu():
     """Without a device the product path must fail loudly, never compute on the CPU."""
     from gaussian_process_amd import _lib

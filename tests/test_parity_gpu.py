@@ -1171,21 +1171,16 @@ def test_fit_predict_one_pass_matches_two_calls(ctx, oracle, N, d, n):
     a2, m2, d2 = ctx.alpha(), ctx.m(), ctx.diag()
     P2 = ctx.post_chol(1e-6) if n <= 1024 else None
     scale = max(1.0, np.abs(a2).max() * 1e-3)
-    for form in (1, 2, 0):          # the rows ride inside the launches / follow on their own stream / chosen by size
-        ctx.set_option("one_pass_form", form)
-        try:
-            lml1, mu1, var1 = ctx.fit_predict(X, y, Xs, 1.0, 2.0, 5e-4, want_sd=False)
-            assert lml1 == lml2
-            assert np.array_equal(ctx.m(), m2) and np.array_equal(ctx.diag(), d2) and np.array_equal(ctx.alpha(), a2)
-            assert np.max(np.abs(mu1 - mu2)) <= 1e-11 * scale, (form, np.max(np.abs(mu1 - mu2)))
-            assert np.max(np.abs(var1 - var2)) <= 1e-12, (form, np.max(np.abs(var1 - var2)))
-            if P2 is not None:
-                P1 = ctx.post_chol(1e-6)
-                assert np.max(np.abs(P1 - P2)) <= 1e-7 * max(1.0, np.abs(P2).max())     # the factor of a matrix of ~1e-6 pivots
-            lml1b, mu1b, var1b = ctx.fit_predict_resident(1.0, 2.0, 5e-4, want_sd=False)
-            assert lml1b == lml1 and np.array_equal(mu1b, mu1) and np.array_equal(var1b, var1)      # deterministic
-        finally:
-            ctx.set_option("one_pass_form", 0)
+    lml1, mu1, var1 = ctx.fit_predict(X, y, Xs, 1.0, 2.0, 5e-4, want_sd=False)     # the rows ride inside the launches
+    assert lml1 == lml2
+    assert np.array_equal(ctx.m(), m2) and np.array_equal(ctx.diag(), d2) and np.array_equal(ctx.alpha(), a2)
+    assert np.max(np.abs(mu1 - mu2)) <= 1e-11 * scale, np.max(np.abs(mu1 - mu2))
+    assert np.max(np.abs(var1 - var2)) <= 1e-12, np.max(np.abs(var1 - var2))
+    if P2 is not None:
+        P1 = ctx.post_chol(1e-6)
+        assert np.max(np.abs(P1 - P2)) <= 1e-7 * max(1.0, np.abs(P2).max())     # the factor of a matrix of ~1e-6 pivots
+    lml1b, mu1b, var1b = ctx.fit_predict_resident(1.0, 2.0, 5e-4, want_sd=False)
+    assert lml1b == lml1 and np.array_equal(mu1b, mu1) and np.array_equal(var1b, var1)      # deterministic
     lml3 = ctx.factorize(1.0, 2.0, 5e-4)
     mu3, var3 = ctx.predict_resident(want_sd=False)
     assert lml3 == lml2 and np.array_equal(mu3, mu2) and np.array_equal(var3, var2)

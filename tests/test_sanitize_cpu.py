@@ -42,7 +42,7 @@ def test_c_abi_header_is_plain_c_and_cxx(tmp_path, lang, std):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_host_planners_under_asan_ubsan(tmp_path):
     """The product's host-side launch planning (gaussian_process_amd/csrc/gpmi_plan.h: supertile / triangular / staircase
-    enumeration with its fixed prefix table, live-tile tests, block-width schedules, the bench line's flop counts) is the
+    enumeration with its fixed prefix table, live-tile tests, the bench line's flop counts) is the
     same header the kernels are compiled from; here plain g++ builds it with AddressSanitizer + UBSan and
     tests/sanitize/plan_check.cpp holds ~16 000 plans against brute force: every live tile enumerated exactly once, no
     dead one, M up to 131072, every supertile edge, ragged sizes, a staircase one row too tall for its table."""
