@@ -67,6 +67,7 @@ SIGNATURES = {
     "gpmi_lml_grad": [_vp, _dp, _dp],
     "gpmi_set_lengthscales": [_vp, _dp, _i64],
     "gpmi_lml_grad_ard": [_vp, _dp, _dp, _dp, _dp],
+    "gpmi_lml_grad_co2": [_vp, _dp, _dp],
     "gpmi_loo": [_vp, _dp, _dp, _dp, _dp],
     "gpmi_loo_grad": [_vp, _dp, _dp, _dp],
     "gpmi_grad_trace": [_vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, _dp, _dp, _dp, _dp],

@@ -517,6 +517,14 @@ int gpmi_lml_grad_ard(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     return lml_grad_ard_impl(c, d_r, d_ell, d_sigma, d_noise);
 }
 
+int gpmi_lml_grad_co2(gpmi_ctx* c, double* d_theta, double* d_noise) {
+    if (!c) return fail_arg("gpmi_lml_grad_co2: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    return lml_grad_co2_impl(c, d_theta, d_noise);
+}
+
 int gpmi_loo(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo) {
     if (!c) return fail_arg("gpmi_loo: null context");
     HIP_TRY(hipSetDevice(c->device));

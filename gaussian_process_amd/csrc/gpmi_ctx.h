@@ -333,6 +333,7 @@ int predict_front(gpmi_ctx* c, int ks_slot);
 int predict_resident_impl(gpmi_ctx* c, double* mu, double* out2, int want_sd);
 int lml_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma);
 int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
+int lml_grad_co2_impl(gpmi_ctx* c, double* d_theta, double* d_noise);
 int loo_impl(gpmi_ctx* c, double* mu, double* var, double* logp, double* loo);
 int loo_grad_impl(gpmi_ctx* c, double* d_ell, double* d_sigma, double* d_noise);
 int grad_trace_impl(gpmi_ctx* c, const double* a_in, const double* b_in, int64_t N, int64_t d, double sigma, double ell,

@@ -224,6 +224,23 @@ int64_t grad_ard_blocks(const GradArdArgs& a);
 int64_t grad_ard_width(const GradArdArgs& a);
 int64_t grad_ard_launches(const GradArdArgs& a);
 hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a);
+// The same W against the eleven basis sums of the CO2 composite kernel (kind 3) over the lower 128 x 128 tiles of Kn:
+//   sums[0..10] = S1 .. S11 of grad.hip's grad_co2_kernel, plain (the caller scales them into the twelve derivatives),
+// each the fixed-order sum of the per-block partials.  The constants multiply sq, sin^2(pi r) and log1p(u) inside the four
+// exponentials: n1 = -1 / (2 theta_2^2), n4 = -1 / (2 theta_4^2), n5 = -2 / theta_5^2, cu = 1 / (2 theta_8 theta_7^2),
+// n8 = -theta_8, n10 = -1 / (2 theta_10^2).
+struct GradCo2Args {
+    const double* Z;          // inputs n x d (device)
+    int64_t n, d;
+    const double* alpha;      // length n
+    const double* Kn;         // -K_y^-1, lower tiles valid, leading dimension ld
+    int64_t ld;
+    double n1, n4, n5, cu, n8, n10;
+    double* partial;          // 11 * grad_co2_blocks doubles, component-major
+    double* sums;             // 11 doubles
+};
+int64_t grad_co2_blocks(const GradCo2Args& a);
+hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a);
 // Z[i][k] = X[i][k] / r[k]: one IEEE division per element
 hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z);
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n);

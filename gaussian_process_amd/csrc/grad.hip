@@ -340,6 +340,125 @@ __global__ __launch_bounds__(256) void ard_reduce_kernel(const double* partial, 
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
+// ---- 11 basis sums of the CO2 composite kernel (kind 3; CO2_example.py:9-64) ----------------------------------------
+// A sibling of grad_ard_kernel: the same lower-tile enumeration over Kn = -K_y^-1, the same columns and rows per thread,
+// the same weight w = alpha_i alpha_j + Kn_ij (strictly-lower elements twice), the same reduction orders and
+// ard_reduce_kernel behind it.  Per element, with sq the squared distance and r = sqrt(sq):
+//     e1 = exp(n1 sq)   s2 = sin^2(pi r)   q2 = exp(n4 sq + n5 s2)   u = cu sq   p3 = exp(n8 log1p(u))   e4 = exp(n10 sq)
+//     S1 += w e1   S2 += w e1 sq   S3 += w q2   S4 += w q2 sq   S5 += w q2 s2
+//     S6 += w p3   S7 += w p3 sq / (1 + u)   S8 += w p3 (u / (1 + u) - log1p(u))   S9 += w e4   S10 += w e4 sq
+//     S11 += w on the diagonal
+// The six constants come from the host (regress.hip: lml_grad_co2_impl), which also turns the sums into the twelve
+// derivatives.  Every term is regular at sq == 0 (e1 = 1, s2 = 0, u = 0): nothing is selected on the diagonal or for
+// duplicate points.  LDS: d <= GRAD_MAXD, both tile edges staged as in grad_trace_kernel; beyond, X comes from global
+// memory.  Accumulators are named by compile-time constants only.
+constexpr int CO2_NS = 11;
+
+struct Co2Dev {
+    const double* Z;
+    int64_t n;
+    int d;
+    const double* alpha;
+    const double* Kn;
+    int64_t ld;
+    double n1, n4, n5, cu, n8, n10;
+    double* partial;
+    int64_t nblk;
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void grad_co2_kernel(const Co2Dev p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red[4][CO2_NS];
+    const int s = blockIdx.x;
+    int ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
+    while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
+    while (ti * (ti + 1) / 2 > s) --ti;
+    const int tj = s - ti * (ti + 1) / 2;
+    const int d = p.d;
+    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
+    const int tid = threadIdx.x;
+    double* As = lds;               // [RT][d]
+    double* Bs = lds + RT * d;      // [d][RT]
+    if (LDS) {
+        for (int e = tid; e < RT * d; e += 256) {
+            const int r = e / d, k = e - r * d;
+            const int64_t ga = grow0 + r, gb = gcol0 + r;
+            As[r * d + k] = (ga < p.n) ? p.Z[ga * d + k] : 0.0;
+            Bs[k * RT + r] = (gb < p.n) ? p.Z[gb * d + k] : 0.0;
+        }
+        __syncthreads();
+    }
+    const int cp = tid & 63, rg = tid >> 6;
+    const int64_t gc = gcol0 + cp;      // the thread's columns: gc and gc + 64
+    double acc[CO2_NS];
+#pragma unroll
+    for (int k = 0; k < CO2_NS; ++k) acc[k] = 0.0;
+    for (int r = 0; r < 32; ++r) {
+        const int lr = 32 * rg + r;
+        const int64_t gr = grow0 + lr;
+        if (gr >= p.n) break;                                    // wave-uniform
+        const double ar_ = p.alpha[gr];
+        const double* kp = p.Kn + gr * p.ld + gc;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int64_t g = gc + 64 * c;
+            const bool in = g < p.n;
+            double sq = 0.0;
+            if (LDS) {
+                const double* ar = &As[lr * d];
+                const double* bc = &Bs[cp + 64 * c];
+                for (int k = 0; k < d; ++k) {
+                    const double e = ar[k] - bc[k * RT];
+                    sq = fma(e, e, sq);
+                }
+            } else {
+                const double* ar = p.Z + gr * d;
+                const double* b = p.Z + (in ? g : 0) * d;
+                for (int k = 0; k < d; ++k) {
+                    const double e = ar[k] - b[k];
+                    sq = fma(e, e, sq);
+                }
+            }
+            // Kn holds -K_y^-1, valid on and below the diagonal only
+            double w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
+            if (g == gr) acc[10] += w;
+            else w += w;
+            const double sn = sin(M_PI * sqrt(sq));
+            const double s2 = sn * sn;
+            const double u = p.cu * sq;
+            const double l1p = log1p(u);
+            const double rc = 1.0 / (1.0 + u);
+            const double w1 = w * exp(p.n1 * sq);
+            const double w2 = w * exp(fma(p.n4, sq, p.n5 * s2));
+            const double w3 = w * exp(p.n8 * l1p);
+            const double w4 = w * exp(p.n10 * sq);
+            acc[0] += w1;
+            acc[1] = fma(w1, sq, acc[1]);
+            acc[2] += w2;
+            acc[3] = fma(w2, sq, acc[3]);
+            acc[4] = fma(w2, s2, acc[4]);
+            acc[5] += w3;
+            acc[6] = fma(w3, sq * rc, acc[6]);
+            acc[7] = fma(w3, u * rc - l1p, acc[7]);
+            acc[8] += w4;
+            acc[9] = fma(w4, sq, acc[9]);
+        }
+    }
+    // 64 lanes by a butterfly, then the four waves in order: the same order every run
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < CO2_NS; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (cp == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (tid < CO2_NS)
+        p.partial[(int64_t)tid * p.nblk + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
 __global__ void scale_inputs_kernel(const double* X, const double* r, int64_t total, int d, double* Z) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) Z[i] = X[i] / r[i % d];
@@ -644,6 +763,26 @@ hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+int64_t grad_co2_blocks(const GradCo2Args& a) {
+    const int64_t T = (a.n + RT - 1) / RT;
+    return T * (T + 1) / 2;
+}
+
+hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a) {
+    if (a.n <= 0 || a.d <= 0) return hipSuccess;
+    Co2Dev p;
+    p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld;
+    p.n1 = a.n1; p.n4 = a.n4; p.n5 = a.n5; p.cu = a.cu; p.n8 = a.n8; p.n10 = a.n10;
+    p.partial = a.partial; p.nblk = grad_co2_blocks(a);
+    const dim3 grid((unsigned)p.nblk), block(256);
+    if (a.d <= GRAD_MAXD) hipLaunchKernelGGL(grad_co2_kernel<true>, grid, block, (size_t)2 * RT * a.d * sizeof(double), s, p);
+    else hipLaunchKernelGGL(grad_co2_kernel<false>, grid, block, 0, s, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ard_reduce_kernel, dim3(CO2_NS), dim3(256), 0, s, a.partial, p.nblk, a.sums);
+    return hipGetLastError();
 }
 
 int64_t grad_trace_blocks(const GradArgs& a) {

@@ -223,6 +223,55 @@ int lml_grad_ard_impl(gpmi_ctx* c, double* d_r, double* d_ell, double* d_sigma, 
     return GPMI_OK;
 }
 
+// The gradient of the CO2 composite kernel (kind 3; GPML section 5.4.3): the 11 hyper-parameters and the noise variance
+// from eleven basis sums of the same W in one fused pass (grad.hip: grad_co2_kernel).  alpha, U and -K_y^-1 are formed
+// exactly as in lml_grad_impl.  With K = theta_1^2 e1 + theta_3^2 q2 + theta_6^2 p3 + theta_9^2 e4 + theta_11^2 delta and
+// g_m = .5 sum_ij W_ij dK_ij/dtheta_m the per-element constants are formed here in double and the sums scaled here.
+int lml_grad_co2_impl(gpmi_ctx* c, double* d_theta, double* d_noise) {
+    if (c->res.regression() && c->kind != 3)
+        return fail_arg("gpmi_lml_grad_co2: CO2 composite kernel only (kind 3; gpmi_set_kernel_params)");
+    double* alpha = nullptr;
+    size_t sp = 0;
+    int rc = grad_front(c, "gpmi_lml_grad_co2: no regression factorisation resident (call gpmi_factorize)",
+                        nullptr /* the kind is checked above */, GPMI_T_GRAD, true, &alpha, &sp);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const double* th = c->kpv;             // th[i] = theta_(i+1)
+    GradCo2Args a;
+    a.Z = c->x_train(); a.n = c->N; a.d = c->d;
+    a.alpha = alpha; a.Kn = c->Kn.as<double>(); a.ld = c->ldA;
+    a.n1 = -1.0 / (2.0 * th[1] * th[1]);
+    a.n4 = -1.0 / (2.0 * th[3] * th[3]);
+    a.n5 = -2.0 / (th[4] * th[4]);
+    a.cu = 1.0 / (2.0 * th[7] * (th[6] * th[6]));
+    a.n8 = -th[7];
+    a.n10 = -1.0 / (2.0 * th[9] * th[9]);
+    HIP_TRY(c->gpart.ensure((size_t)grad_co2_blocks(a) * 11 * 8));
+    HIP_TRY(c->gsum.ensure(11 * 8));
+    a.partial = c->gpart.as<double>();
+    a.sums = c->gsum.as<double>();
+    HIP_TRY(launch_grad_co2(s, a));
+    c->span_end(sp);
+    double S[11];
+    HIP_TRY(hipMemcpyAsync(S, a.sums, sizeof S, hipMemcpyDeviceToHost, s));
+    if ((rc = solve_epilogue(c, "gpmi_lml_grad_co2"))) return rc;
+    if (d_theta) {
+        d_theta[0] = th[0] * S[0];
+        d_theta[1] = .5 * (th[0] * th[0]) * S[1] / (th[1] * th[1] * th[1]);
+        d_theta[2] = th[2] * S[2];
+        d_theta[3] = .5 * (th[2] * th[2]) * S[3] / (th[3] * th[3] * th[3]);
+        d_theta[4] = 2.0 * (th[2] * th[2]) * S[4] / (th[4] * th[4] * th[4]);
+        d_theta[5] = th[5] * S[5];
+        d_theta[6] = .5 * (th[5] * th[5]) * S[6] / (th[6] * th[6] * th[6]);
+        d_theta[7] = .5 * (th[5] * th[5]) * S[7];
+        d_theta[8] = th[8] * S[8];
+        d_theta[9] = .5 * (th[8] * th[8]) * S[9] / (th[9] * th[9] * th[9]);
+        d_theta[10] = th[10] * S[10];
+    }
+    if (d_noise) *d_noise = .5 * S[10];
+    return GPMI_OK;
+}
+
 // Leave-one-out cross-validation at the resident factorisation (GPML section 5.4.2, eqs. 5.10-5.12): with alpha =
 // K_y^-1 y and kappa_i = [K_y^-1]_ii the prediction of y_i from the other N - 1 points is N(y_i - alpha_i / kappa_i,
 // 1 / kappa_i).  alpha and U = L^-T as in lml_grad_impl; kappa_i is the squared norm of row i of U (K_y^-1 = U U^T), so

@@ -390,6 +390,15 @@ class GPContext:
         check(self._lib.gpmi_lml_grad_ard(self._h, ptr(d_r), C.byref(dl), C.byref(ds), C.byref(dn)))
         return d_r, dl.value, ds.value, dn.value
 
+    def lml_grad_co2(self):
+        """(d_theta (11,), dLML/dnoise_var) at the resident factorisation of the CO2 composite kernel ('co2'): the
+        derivatives w.r.t. the 11 hyper-parameters of CO2_example.py's covariance_function and the noise variance, from
+        one fused pass over K_y^-1 (gpmi_lml_grad_co2)."""
+        d_theta = np.empty(11)
+        dn = C.c_double()
+        check(self._lib.gpmi_lml_grad_co2(self._h, ptr(d_theta), C.byref(dn)))
+        return d_theta, dn.value
+
     # ---- leave-one-out cross-validation (GPML 5.4.2) ------------------------------------
     def loo(self):
         """(mu (N,), var (N,), logp (N,), loo) at the resident regression factorisation: mean and variance of every

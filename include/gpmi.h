@@ -263,6 +263,27 @@ int gpmi_set_lengthscales(gpmi_ctx* ctx, const double* r, int64_t d);
  * Any output may be NULL.  sum_k r_k d_r[k] == l * d_ell (K depends on l * r_k only).  Refuses what gpmi_lml_grad
  * refuses.  One fused pass over K_y^-1 per 32 dimensions; the sums are bitwise reproducible from run to run. */
 int gpmi_lml_grad_ard(gpmi_ctx* ctx, double* d_r, double* d_ell, double* d_sigma, double* d_noise);
+/* The gradient of the log marginal likelihood of the CO2 composite kernel (kind 3, gpmi_set_kernel_params) w.r.t. its
+ * 11 hyper-parameters and the noise variance at the resident factorisation (GPML section 5.4.3).  With
+ * W = alpha alpha^T - K_y^-1, sq_ij the squared distance, r = sqrt(sq) and
+ *   e1 = exp(-sq / (2 theta_2^2))                                    K = theta_1^2 e1 + theta_3^2 q2 + theta_6^2 p3
+ *   q2 = exp(-sq / (2 theta_4^2) - 2 sin^2(pi r) / theta_5^2)            + theta_9^2 e4 + theta_11^2 delta_ij
+ *   p3 = (1 + u)^-theta_8,  u = sq / (2 theta_8 theta_7^2)
+ *   e4 = exp(-sq / (2 theta_10^2))
+ * d_theta[m] = .5 * sum_ij W_ij dK_ij/dtheta_(m+1)  (11 doubles):
+ *   dK/dtheta_1 = 2 theta_1 e1               dK/dtheta_2 = theta_1^2 e1 sq / theta_2^3
+ *   dK/dtheta_3 = 2 theta_3 q2               dK/dtheta_4 = theta_3^2 q2 sq / theta_4^3
+ *   dK/dtheta_5 = 4 theta_3^2 q2 sin^2(pi r) / theta_5^3
+ *   dK/dtheta_6 = 2 theta_6 p3               dK/dtheta_7 = theta_6^2 p3 sq / (theta_7^3 (1 + u))
+ *   dK/dtheta_8 = theta_6^2 p3 (u / (1 + u) - log(1 + u))
+ *   dK/dtheta_9 = 2 theta_9 e4               dK/dtheta_10 = theta_9^2 e4 sq / theta_10^3
+ *   dK/dtheta_11 = 2 theta_11 delta_ij
+ * *d_noise = .5 * (alpha^T alpha - trace(K_y^-1)) = d_theta[10] / (2 theta_11).  Either output may be NULL.
+ * GPMI_ERR_BAD_ARG when no regression factorisation is resident or the context's kernel is not kind 3.  Reads the
+ * resident fit only: alpha, prediction, posterior samples and leave-one-out work afterwards as before (gpmi_append
+ * refuses kind 3 before and after).  Costs what gpmi_lml_grad costs plus one fused pass over K_y^-1; the sums are bitwise
+ * reproducible from run to run.  The derivatives assume 1 + u > 0 (theta_8 > 0). */
+int gpmi_lml_grad_co2(gpmi_ctx* ctx, double* d_theta, double* d_noise);
 /* Leave-one-out cross-validation at the resident regression factorisation (Rasmussen & Williams, GPML, section 5.4.2,
  * eqs. 5.10-5.12).  With K_y = K + noise_var I, alpha = K_y^-1 y and kappa_i = [K_y^-1]_ii:
  *   mu[i]   = y_i - alpha_i / kappa_i,  var[i] = 1 / kappa_i      (mean and variance of y_i predicted from the other
