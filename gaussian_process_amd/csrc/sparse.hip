@@ -23,6 +23,7 @@
 // the lower triangle has few tiles; each workgroup writes its partial tile, and gram_reduce_kernel adds the partials onto
 // B in index order: no atomics, the same bits every run.
 #include "gpmi_ctx.h"
+#include "gpmi_sparse_plan.h"
 #include "lap_dev.h"
 
 namespace gpmi {
@@ -36,8 +37,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr int GK = 16;                         // slab rows per LDS stage
 constexpr int GRAM_LDS = 2 * 2 * GK * TILE * 8;   // two stages of two operand strips
-constexpr int64_t GRAM_TARGET_GROUPS = 1024;   // workgroups a launch aims at: four per CU of a 256-CU chip
-constexpr int64_t DEFAULT_SLAB = 16384;
+static_assert(SPARSE_TILE == TILE, "gpmi_sparse_plan.h plans in the tiles of the kernels");
 
 // fixed-order sum over a workgroup of 256 threads; the result is valid in every thread
 __device__ __forceinline__ double wg_sum256(double v, double* sh) {
@@ -228,21 +228,7 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restri
     }
 }
 
-// The launch plan of the Gram kernel, a function of the shapes alone: the slab's rows are cut into nsplit chunks of
-// `chunk` rows (a multiple of 128; the last may be shorter) so that tiles x splits reaches GRAM_TARGET_GROUPS where the
-// slab has the rows for it.  One lower tile (m <= 128) and a slab of 256 rows already give two splits.
-struct GramPlan { int64_t ntiles, nsplit, chunk; };
-GramPlan gram_plan(int64_t rows, int64_t mp) {
-    const int64_t nt = mp / TILE, units = rows / TILE;
-    GramPlan p;
-    p.ntiles = nt * (nt + 1) / 2;
-    const int64_t want = (GRAM_TARGET_GROUPS + p.ntiles - 1) / p.ntiles;
-    int64_t ns = std::min(units, want);
-    const int64_t cu = (units + ns - 1) / ns;
-    p.nsplit = (units + cu - 1) / cu;
-    p.chunk = cu * TILE;
-    return p;
-}
+// The launch plan of the Gram kernel (how many splits, of how many rows each) is gram_plan of gpmi_sparse_plan.h.
 
 // ---- the gradient of the VFE bound -----------------------------------------------------------------------------------
 // With u = L_B^-T c, p = L^-T u, T = L^-T (I - B^-1) L^-1 / s, beta = (y - K_fu p) / s and
@@ -413,10 +399,7 @@ __global__ __launch_bounds__(256) void sparse_grad_final_kernel(const double* __
 
 }  // namespace
 
-int64_t gram_part_doubles(int64_t rows, int64_t mp) {
-    const GramPlan p = gram_plan(rows, mp);
-    return p.ntiles * p.nsplit * TILE * TILE;
-}
+int64_t gram_part_doubles(int64_t rows, int64_t mp) { return gram_plan_doubles(rows, mp); }
 
 hipError_t launch_gram_tn(hipStream_t s, const double* V, int64_t ldv, int64_t rows, int64_t mp, double* part, double* B,
                           int64_t ldb) {
@@ -447,7 +430,8 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     hipStream_t st = c->stream;
     const int64_t N = c->N, d = c->d, Np = round_up(N, TILE);
     const int64_t mp = round_up(m, TILE), ldm = mp + c->ld_pad;
-    const int64_t S = std::min(Np, c->sparse_slab ? round_up(c->sparse_slab, TILE) : DEFAULT_SLAB);
+    const SparseSlabs slabs = sparse_slabs(N, c->sparse_slab, mp);      // gpmi_sparse_plan.h
+    const int64_t S = slabs.S;
     c->res.drop_fit();
     c->timers_reset({GPMI_T_SPARSE, GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR, GPMI_T_POSTCHOL, GPMI_T_CHOL});
     c->sig2 = sigma * sigma;
@@ -471,10 +455,9 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     HIP_TRY(hipStreamSynchronize(st));           // Z is the caller's buffer
     const double* Zd = c->sp_Z.as<double>();
 
-    // the last slab is shorter, and a shorter slab can have MORE splits than a full one (the chunk length is rounded)
-    const int64_t last_rows = Np % S ? Np % S : S;
-    const int64_t part_doubles = std::max(gram_part_doubles(S, mp), gram_part_doubles(last_rows, mp));
-    const int64_t gemv_doubles = ((S + 63) / 64) * mp;
+    // the workspaces of the Gram kernel and of the matrix-vector product are sized for every slab of the fit: the last
+    // slab is shorter, and a shorter slab can have MORE splits than a full one
+    const int64_t part_doubles = slabs.part_doubles, gemv_doubles = slabs.gemv_doubles;
     // sp_vec: g | the slab's g | y~ | the rows' partials [3][S] | acc[4] | red[4] | rec[8]
     HIP_TRY(c->sp_L.ensure((size_t)mp * ldm * 8));
     HIP_TRY(c->sp_B.ensure((size_t)(mp + TILE) * ldm * 8));
