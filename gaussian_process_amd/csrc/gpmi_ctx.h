@@ -319,7 +319,8 @@ int alpha_impl(gpmi_ctx* c, double* alpha_out);
 // vec made large enough, then inside a span of that slot, which it opens: (alpha_out not null) alpha = L^-T m,
 // U = L^-T by the TRSM sweep on the identity and (want_kn) Kn = -U U^T on the lower tiles
 int factor_inverse_front(gpmi_ctx* c, int slot, bool want_kn, double** alpha_out, size_t* span);
-// The ending of the three ARD traces (gpmi_lml_grad_ard, gpmi_laplace_grad, gpmi_softmax_grad).  grad_ard_finish, given
+// The ending of the three ARD traces (gpmi_lml_grad_ard, gpmi_laplace_grad, gpmi_softmax_grad; regress.hip's
+// tile_sums_finish, in which gpmi_lml_grad_co2 ends too).  grad_ard_finish, given
 // the arguments with the caller's inputs: gpart and gsum sized, the trace, the span's end, the launches' plain sums on the
 // host behind the call's one synchronisation, timers collected; solve_api not null: a backward solve ran in this call and
 // its give-up word is read and reported under that name.  grad_ard_scale: the derivatives asked for (null: skipped) from

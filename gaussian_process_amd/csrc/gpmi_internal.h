@@ -198,6 +198,8 @@ struct GradArgs {
     int tri;                  // 1: symmetric case, lower tiles only (needs row0 == 0, nrows == nB)
     double* partial;          // 2 doubles per block (grad_trace_blocks of them)
 };
+// the lower 128 x 128 tiles of an n x n matrix: the blocks of a tri launch and of the ARD and CO2 sums
+int64_t tri_tile_count(int64_t n);
 int64_t grad_trace_blocks(const GradArgs& a);
 hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a);
 // The same W against d + 3 derivatives (per-dimension lengthscales, l, sigma, noise) over the lower 128 x 128 tiles of
@@ -212,7 +214,7 @@ struct GradArdArgs {
     int64_t ld;
     double coef;              // -1 / (2 l^2); family > 0: -a
     int family = 0;           // cov_family of the kernel: the "x" of the sums is then H(t) and sums[width + 1] takes K / sigma^2
-    double* partial;          // (width + 3) * grad_ard_blocks doubles, component-major
+    double* partial;          // (width + 3) * tri_tile_count(n) doubles, component-major
     double* sums;             // (width + 3) * grad_ard_launches doubles
     // The binary classifier's gradient (gpmi_laplace_grad; family 0 only): with lap_s set, alpha is a, Kn is -B^-1 and
     // the weight is a_i a_j + s_i s_j Kn_ij + z_i g_j + z_j g_i; there is no noise sum (its slot holds 0)
@@ -220,7 +222,6 @@ struct GradArdArgs {
     const double* lap_z = nullptr;
     const double* lap_g = nullptr;
 };
-int64_t grad_ard_blocks(const GradArdArgs& a);
 int64_t grad_ard_width(const GradArdArgs& a);
 int64_t grad_ard_launches(const GradArdArgs& a);
 hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a);
@@ -236,10 +237,9 @@ struct GradCo2Args {
     const double* Kn;         // -K_y^-1, lower tiles valid, leading dimension ld
     int64_t ld;
     double n1, n4, n5, cu, n8, n10;
-    double* partial;          // 11 * grad_co2_blocks doubles, component-major
+    double* partial;          // 11 * tri_tile_count(n) doubles, component-major
     double* sums;             // 11 doubles
 };
-int64_t grad_co2_blocks(const GradCo2Args& a);
 hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a);
 // Z[i][k] = X[i][k] / r[k]: one IEEE division per element
 hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z);

@@ -21,8 +21,8 @@ constexpr int RBF_TILE = 128;          // tile edge of every K-build kernel
 constexpr int RBF_LDS_MAXD = 32;       // largest d staged in LDS; above: straight from global memory
 constexpr int64_t RBF_STRIP_MIN_TILES = 4096;   // launches of at least this many tiles: 4 row tiles per work item
 
-// Triangular tile enumeration of the symmetric build: linear index s = ti (ti + 1) / 2 + tj, 0 <= tj <= ti.  The float
-// square root is a first guess only; the two loops make the answer exact for every s whose successor triangle number
+// Triangular tile enumeration of the symmetric build, and of the gradient kernels (grad.hip): linear index
+// s = ti (ti + 1) / 2 + tj, 0 <= tj <= ti.  The float square root is a first guess only; the two loops make the answer exact for every s whose successor triangle number
 // fits an int (ti <= 46339, far above the 1024 row tiles of N = 131072).
 GPMI_KROUTE_HD inline void rbf_tri_tile(int s, int& ti, int& tj) {
     ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);

@@ -10,19 +10,24 @@
 // D_ij is recomputed from X (as in the K build), W_ij = alpha_i alpha_j - Kinv_ij
 // reads Kinv once.  HBM-read bound: 8 B per element.
 //
-// One 128 x 128 tile per block, a column pair x 32 rows per thread, X tiles in LDS
-// (d <= 32) or straight from global memory; per-block partial sums, reduced in a
-// fixed order (bitwise reproducible); the host adds the per-tile partials in order.
+// Every tile kernel here (grad_trace_kernel, grad_ard_kernel, grad_co2_kernel, loo_dmat_kernel) recomputes the kernel
+// element from X and multiplies it by a weight: one 128 x 128 tile per block, two columns x 32 rows per thread.  What
+// they share exists once, below:
+//   rbf_tri_tile (gpmi_kroute.h) the lower tiles of a symmetric matrix from the block index
+//   stage_edges               both tile edges of X into LDS (d <= 32), zero past the end; beyond, X comes from global memory
+//   sqdist2 / sqdist1         the squared distance, s = fma(e, e, s) over k ascending, from LDS or global memory
+//   wave_sum64, block_tree256, block_partials   the reductions, each in ONE fixed order: results are bitwise reproducible
+//   lower_tile_sums           the body of the weighted sums over the lower tiles of Kn = -K_y^-1 (ARD, Laplace, CO2)
+// A kernel's own comment says only what is particular to it: its weight, its terms, its column layout.
 //
-// The three "recompute the kernel element from X, multiply by a weight" kernels (grad_trace_kernel, grad_ard_kernel,
-// loo_dmat_kernel) take the per-element function as a compile-time family F (cov_family: 0 squared exponential,
-// 1 / 2 / 3 Matern nu = 1/2, 3/2, 5/2).  For a Matern, with t = a sqrt(sq), a = -coef:
+// The per-element function is a compile-time family F (cov_family: 0 squared exponential, 1 / 2 / 3 Matern nu = 1/2,
+// 3/2, 5/2).  For a Matern, with t = a sqrt(sq), a = -coef:
 //     K / sigma^2 = P(t) e^-t,   dK/dl = sigma^2 a^2 H(t) sq / l,   dK/dz-scale_k likewise with (z_ik - z_jk)^2,
 //     H(t) = -(1/t) d(P e^-t)/dt = e^-t / t,  e^-t,  (1 + t) e^-t / 3
 // H_1/2 is singular at t = 0 but always multiplied by a squared difference <= sq: it is SELECTED to 0 there (duplicate
-// training points), never divided.  Tile enumeration, staging, accumulators and reduction orders are the same for
-// every family, and the family-0 instantiations are the code they were before the families existed.
+// training points), never divided.
 #include <algorithm>
+#include <type_traits>
 
 #include "exp_dev.h"
 #include "gpmi_internal.h"
@@ -34,6 +39,110 @@ namespace {
 constexpr int RT = 128;
 constexpr int GRAD_MAXD = 32;
 
+// ---- the shared pieces ------------------------------------------------------------------------------------------------
+// As[r][k] = A[arow0 + r][k] and Bs[k][r] = B[bcol0 + r][k] for the RT rows behind either origin, zero past nA / nB.
+// DC == 0: LDS rows are d wide.  DC > 0 (the ARD kernel): they are DC >= d wide and zero from d on.
+template <int DC>
+__device__ __forceinline__ void stage_edges(double* As, double* Bs, const double* A, const double* B, int64_t arow0,
+                                            int64_t bcol0, int64_t nA, int64_t nB, int d, int tid) {
+    const int w = DC ? DC : d;
+    for (int e = tid; e < RT * w; e += 256) {
+        const int r = e / w, k = e - r * w;
+        const int64_t ga = arow0 + r, gb = bcol0 + r;
+        const bool ink = DC == 0 || k < d;
+        As[r * w + k] = (ink && ga < nA) ? A[ga * d + k] : 0.0;
+        Bs[k * RT + r] = (ink && gb < nB) ? B[gb * d + k] : 0.0;
+    }
+    __syncthreads();
+}
+
+// Squared distances of row a to the columns b0 and b1, whose dimension k lies at [k * sb] (LDS: sb = RT, b1 = b0 + 1;
+// global memory: sb = 1)
+__device__ __forceinline__ void sqdist2(const double* a, const double* b0, const double* b1, int sb, int d, double& s0,
+                                        double& s1) {
+    for (int k = 0; k < d; ++k) {
+        const double ak = a[k];
+        const double e0 = ak - b0[k * sb], e1 = ak - b1[k * sb];
+        s0 = fma(e0, e0, s0);
+        s1 = fma(e1, e1, s1);
+    }
+}
+
+// ... and to the one column b
+__device__ __forceinline__ double sqdist1(const double* a, const double* b, int sb, int d) {
+    double sq = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double e = a[k] - b[k * sb];
+        sq = fma(e, e, sq);
+    }
+    return sq;
+}
+
+// The ARD kernel's distance is other arithmetic: the squares e2[k] of the launch's DC dimensions k0 .. k0 + DC are kept
+// and ADDED in order (zero beyond d); from global memory the dimensions outside that window follow by FMA.
+template <int DC, bool LDS>
+__device__ __forceinline__ double ard_sqdist(const double* a, const double* b, int d, int k0, double (&e2)[DC]) {
+    double sq = 0.0;
+#pragma unroll
+    for (int k = 0; k < DC; ++k) {
+        const int kk = k0 + k;
+        const double e = LDS ? a[k] - b[k * RT] : (kk < d) ? a[kk] - b[kk] : 0.0;
+        e2[k] = e * e;
+        sq += e2[k];
+    }
+    if (!LDS) {
+        for (int kk = 0; kk < k0; ++kk) {
+            const double e = a[kk] - b[kk];
+            sq = fma(e, e, sq);
+        }
+        for (int kk = k0 + DC; kk < d; ++kk) {
+            const double e = a[kk] - b[kk];
+            sq = fma(e, e, sq);
+        }
+    }
+    return sq;
+}
+
+// 64 lanes by a butterfly
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// NV values per thread of a 256-thread block by a binary tree in shared memory; sum j ends in sh[j][0], for thread 0 to read
+template <int NV>
+__device__ __forceinline__ void block_tree256(double (&sh)[NV][256], const double (&v)[NV], int tid) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) sh[j][tid] = v[j];
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) sh[j][tid] += sh[j][tid + off];
+        }
+        __syncthreads();
+    }
+}
+
+// NS accumulators per thread to the block's partials, component-major (partial[j * nblk + block]): 64 lanes by the
+// butterfly, then the four waves in order.  ard_reduce_kernel adds the blocks.
+template <int NS>
+__device__ __forceinline__ void block_partials(double (&red)[4][NS], const double (&acc)[NS], int tid, double* partial,
+                                               int64_t nblk) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const double v = wave_sum64(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < NS)
+        partial[(int64_t)tid * nblk + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// ---- two traces: l and sigma ------------------------------------------------------------------------------------------
+// The thread's columns are the adjacent pair 2 cp, 2 cp + 1.  Any row range of a rectangular matrix (tri == 0: the
+// partitioned path) or the lower tiles of the symmetric one; two partials per block, added by the host in block order.
 struct GradDev {
     const double* A;        // rows: nA x d
     const double* B;        // cols: nB x d
@@ -75,11 +184,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
     __shared__ double red[2][256];
     int ti, tj;
     if (p.tri) {
-        const int s = blockIdx.x;
-        ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
-        while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
-        while (ti * (ti + 1) / 2 > s) --ti;
-        tj = s - ti * (ti + 1) / 2;
+        rbf_tri_tile((int)blockIdx.x, ti, tj);
     } else {
         ti = blockIdx.x / p.Tn;
         tj = blockIdx.x - ti * p.Tn;
@@ -90,15 +195,7 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
     const int tid = threadIdx.x;
     double* As = lds;               // [RT][d]
     double* Bs = lds + RT * d;      // [d][RT]
-    if (LDS) {
-        for (int e = tid; e < RT * d; e += 256) {
-            const int r = e / d, k = e - r * d;
-            const int64_t ga = grow0 + r, gb = gcol0 + r;
-            As[r * d + k] = (ga < p.nA) ? p.A[ga * d + k] : 0.0;
-            Bs[k * RT + r] = (gb < p.nB) ? p.B[gb * d + k] : 0.0;
-        }
-        __syncthreads();
-    }
+    if (LDS) stage_edges<0>(As, Bs, p.A, p.B, grow0, gcol0, p.nA, p.nB, d, tid);
     const int cp = tid & 63, rg = tid >> 6;
     const int64_t gc = gcol0 + 2 * cp;
     const double ac0 = (gc < p.nB) ? p.alpha_c[gc] : 0.0;
@@ -109,26 +206,8 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
         const int64_t gr = grow0 + lr;
         if (gr >= p.rend) break;                                 // wave-uniform
         double s0 = 0.0, s1 = 0.0;
-        if (LDS) {
-            const double* ar = &As[lr * d];
-            const double* bc = &Bs[2 * cp];
-            for (int k = 0; k < d; ++k) {
-                const double a = ar[k];
-                const double e0 = a - bc[k * RT], e1 = a - bc[k * RT + 1];
-                s0 = fma(e0, e0, s0);
-                s1 = fma(e1, e1, s1);
-            }
-        } else {
-            const double* ar = p.A + gr * d;
-            const double* b0 = p.B + ((gc < p.nB) ? gc : 0) * d;
-            const double* b1 = p.B + ((gc + 1 < p.nB) ? gc + 1 : 0) * d;
-            for (int k = 0; k < d; ++k) {
-                const double a = ar[k];
-                const double e0 = a - b0[k], e1 = a - b1[k];
-                s0 = fma(e0, e0, s0);
-                s1 = fma(e1, e1, s1);
-            }
-        }
+        if (LDS) sqdist2(&As[lr * d], &Bs[2 * cp], &Bs[2 * cp + 1], RT, d, s0, s1);
+        else sqdist2(p.A + gr * d, p.B + ((gc < p.nB) ? gc : 0) * d, p.B + ((gc + 1 < p.nB) ? gc + 1 : 0) * d, 1, d, s0, s1);
         const double ar_ = p.alpha_r[gr];
         const double* kp = p.Kinv + ((int64_t)ti * RT + lr) * p.ld + gc;
         const double k0 = (gc < p.nB) ? kp[0] : 0.0;
@@ -153,31 +232,85 @@ __global__ __launch_bounds__(256) void grad_trace_kernel(const GradDev p) {
         else acc_l += w0 * (p.sig2 * h0 * (s0 * p.inv_l3)) + w1 * (p.sig2 * h1 * (s1 * p.inv_l3));
         acc_s += w0 * (p.two_sigma * x0) + w1 * (p.two_sigma * x1);
     }
-    red[0][tid] = acc_l;
-    red[1][tid] = acc_s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-            red[0][tid] += red[0][tid + off];
-            red[1][tid] += red[1][tid + off];
-        }
-        __syncthreads();
-    }
+    const double acc[2] = {acc_l, acc_s};
+    block_tree256(red, acc, tid);
     if (tid == 0) {
         p.partial[2 * (size_t)blockIdx.x] = red[0][0];
         p.partial[2 * (size_t)blockIdx.x + 1] = red[1][0];
     }
 }
 
+// ---- weighted sums over the lower tiles of Kn = -K_y^-1 ---------------------------------------------------------------
+// lower_tile_sums is the one body of grad_ard_kernel (regression and Laplace weights) and grad_co2_kernel.  The thread's
+// two columns lie 64 apart (gc and gc + 64), so that a wave reads both tile edges and Kn densely.  Per element it forms the
+// weight w, zero above the diagonal (Kn is valid on and below it only) and doubled strictly below it, then adds the
+// terms of a compile-time terms type T to NS accumulators.  They are indexed by compile-time constants only (every loop
+// over them is unrolled), so they live in registers; block_partials and ard_reduce_kernel sum them.  T supplies:
+//   Dev, NS      the argument block and the number of sums; the last one is the noise slot
+//   DC           LDS row width (0: d)
+//   Weight       the row's share of the weight, loaded once per row, and the element's weight from it
+//   Dist, dist   what the terms need of the squared distance, and its form
+//   add          the terms
+// Nothing here is selected at run time: every difference between the callers is a type or a template parameter.
+
+// w = alpha_i alpha_j + Kn_ij; the diagonal's w goes to the noise sum
+struct RegWeight {
+    double ar;
+    template <class Dev>
+    __device__ __forceinline__ RegWeight(const Dev& p, int64_t gr) : ar(p.alpha[gr]) {}
+    template <class Dev>
+    __device__ __forceinline__ double operator()(const Dev& p, int64_t g, int64_t gr, bool in, const double* kn,
+                                                 double& acc_n) const {
+        double w = (in && g <= gr) ? fma(ar, p.alpha[g], *kn) : 0.0;
+        if (g == gr) acc_n += w;
+        else w += w;
+        return w;
+    }
+};
+
+template <class T, bool LDS>
+__device__ __forceinline__ void lower_tile_sums(const typename T::Dev& p) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red[4][T::NS];
+    int ti, tj;
+    rbf_tri_tile((int)blockIdx.x, ti, tj);
+    const int d = p.d, w = T::DC ? T::DC : d;
+    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
+    const int tid = threadIdx.x;
+    double* As = lds;               // [RT][w]
+    double* Bs = lds + RT * w;      // [w][RT]
+    if (LDS) stage_edges<T::DC>(As, Bs, p.Z, p.Z, grow0, gcol0, p.n, p.n, d, tid);
+    const int cp = tid & 63, rg = tid >> 6;
+    const int64_t gc = gcol0 + cp;
+    double acc[T::NS], acc_n = 0.0;                              // acc_n: the noise sum, the last slot
+#pragma unroll
+    for (int k = 0; k < T::NS; ++k) acc[k] = 0.0;
+    for (int r = 0; r < 32; ++r) {
+        const int lr = 32 * rg + r;
+        const int64_t gr = grow0 + lr;
+        if (gr >= p.n) break;                                    // wave-uniform
+        const typename T::Weight weight(p, gr);
+        const double* kp = p.Kn + gr * p.ld + gc;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {                            // the thread's two columns, one after the other
+            const int64_t g = gc + 64 * c;
+            const bool in = g < p.n;
+            typename T::Dist x;
+            if (LDS) T::template dist<true>(p, &As[lr * w], &Bs[cp + 64 * c], x);
+            else T::template dist<false>(p, p.Z + gr * d, p.Z + (in ? g : 0) * d, x);
+            const double wt = weight(p, g, gr, in, kp + 64 * c, acc_n);
+            T::add(p, wt, x, acc);
+        }
+    }
+    acc[T::NS - 1] = acc_n;
+    block_partials(red, acc, tid, p.partial, p.nblk);
+}
+
 // ---- d + 3 traces: per-dimension lengthscales (ARD), l, sigma, noise ---------------------------------------------
-// A sibling of grad_trace_kernel over the lower tiles of Kn = -K_y^-1 (the same tile enumeration, LDS staging
-// and rows per thread; the thread's two columns lie 64 apart so that a wave reads both edges densely), so that gpmi_lml_grad keeps its bits.  Per element: e_k^2 = (z_ik - z_jk)^2 for the DC dimensions of this
-// launch (zero beyond d), x = exp(coef * sum over ALL d of e_k^2), then
+// Per element: e_k^2 = (z_ik - z_jk)^2 for the DC dimensions of this launch (zero beyond d), x = exp(coef * sum over
+// ALL d of e_k^2), then
 //     acc_k += w x e_k^2,   acc_l += w x sq,   acc_s += w x,   acc_n += w on the diagonal
-// with w = alpha_i alpha_j - K_y^-1_ij, strictly-lower elements counted twice (a Matern family: x = H(t) in acc_k and
-// acc_l, x = P(t) e^-t in acc_s).  The accumulators are indexed by
-// compile-time constants only (every loop over them is unrolled), so they live in registers.  Block partials go out
-// component-major (partial[j * nblk + block]) and are summed by ard_reduce_kernel in a fixed order.
+// with w = alpha_i alpha_j - K_y^-1_ij (a Matern family: x = H(t) in acc_k and acc_l, x = P(t) e^-t in acc_s).
 struct ArdDev {
     const double* Z;
     int64_t n;
@@ -192,9 +325,7 @@ struct ArdDev {
 // The binary classifier's variant (gpmi_laplace_grad): alpha is a, Kn is -B^-1 and the weight of element (i, j) is
 //     w = a_i a_j + s_i s_j Kn_ij + z_i g_j + z_j g_i
 // -- four more vector loads per row and per column, two more multiplications and two more FMAs per element, no noise sum
-// (its slot is written 0).
-// A separate instantiation (LAP, family 0 only) with its own argument block: the regression instantiations are the code
-// they were.
+// (its slot is written 0).  The LAP instantiations (family 0 only) take their own argument block.
 struct ArdLapDev : ArdDev {
     const double* s;
     const double* z;
@@ -203,155 +334,77 @@ struct ArdLapDev : ArdDev {
 template <bool LAP> struct ArdDevOf { typedef ArdDev type; };
 template <> struct ArdDevOf<true> { typedef ArdLapDev type; };
 
+struct LapWeight {
+    double ar, sr, zr, gr_;
+    __device__ __forceinline__ LapWeight(const ArdLapDev& p, int64_t gr)
+        : ar(p.alpha[gr]), sr(p.s[gr]), zr(p.z[gr]), gr_(p.g[gr]) {}
+    __device__ __forceinline__ double operator()(const ArdLapDev& p, int64_t g, int64_t gr, bool in, const double* kn,
+                                                 double&) const {
+        double w = 0.0;
+        if (in && g <= gr) {
+            w = fma(ar, p.alpha[g], (sr * p.s[g]) * *kn);
+            w = fma(zr, p.g[g], w);
+            w = fma(p.z[g], gr_, w);
+        }
+        if (g != gr) w += w;
+        return w;
+    }
+};
+
+template <int DC_, int F, bool LAP>
+struct ArdTerms {
+    typedef typename ArdDevOf<LAP>::type Dev;
+    typedef typename std::conditional<LAP, LapWeight, RegWeight>::type Weight;
+    static constexpr int DC = DC_, NS = DC_ + 3;
+    struct Dist {
+        double sq, e2[DC_];
+    };
+    template <bool LDS>
+    static __device__ __forceinline__ void dist(const Dev& p, const double* a, const double* b, Dist& x) {
+        x.sq = ard_sqdist<DC_, LDS>(a, b, p.d, p.k0, x.e2);
+    }
+    static __device__ __forceinline__ void add(const Dev& p, double w, const Dist& x, double (&acc)[NS]) {
+        double wx, ws;                                           // the weight of the lengthscale sums and of sigma's
+        if constexpr (F == 0) {
+            wx = ws = w * exp(p.coef * x.sq);
+        } else {
+            double kk, hh;
+            matern_kh<F>(p.coef, x.sq, kk, hh);
+            wx = w * hh;
+            ws = w * kk;
+        }
+#pragma unroll
+        for (int k = 0; k < DC_; ++k) acc[k] = fma(wx, x.e2[k], acc[k]);
+        acc[DC_] = fma(wx, x.sq, acc[DC_]);
+        acc[DC_ + 1] += ws;
+    }
+};
+
+// LDS: d <= DC and k0 == 0, dimensions d .. DC are zero on both staged edges
 template <int DC, bool LDS, int F, bool LAP = false>
 __global__ __launch_bounds__(256) void grad_ard_kernel(const typename ArdDevOf<LAP>::type p) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double red[4][DC + 3];
-    const int s = blockIdx.x;
-    int ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
-    while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
-    while (ti * (ti + 1) / 2 > s) --ti;
-    const int tj = s - ti * (ti + 1) / 2;
-    const int d = p.d;
-    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
-    const int tid = threadIdx.x;
-    double* As = lds;               // [RT][DC]
-    double* Bs = lds + RT * DC;     // [DC][RT]
-    if (LDS) {                      // d <= DC, k0 == 0: dimensions d .. DC are zero on both edges
-        for (int e = tid; e < RT * DC; e += 256) {
-            const int r = e / DC, k = e - r * DC;
-            const int64_t ga = grow0 + r, gb = gcol0 + r;
-            As[r * DC + k] = (k < d && ga < p.n) ? p.Z[ga * d + k] : 0.0;
-            Bs[k * RT + r] = (k < d && gb < p.n) ? p.Z[gb * d + k] : 0.0;
-        }
-        __syncthreads();
-    }
-    const int cp = tid & 63, rg = tid >> 6;
-    const int64_t gc = gcol0 + cp;      // the thread's columns: gc and gc + 64 (dense LDS and Kn reads across the wave)
-    double acc[DC];
-#pragma unroll
-    for (int k = 0; k < DC; ++k) acc[k] = 0.0;
-    double acc_l = 0.0, acc_s = 0.0, acc_n = 0.0;
-    for (int r = 0; r < 32; ++r) {
-        const int lr = 32 * rg + r;
-        const int64_t gr = grow0 + lr;
-        if (gr >= p.n) break;                                    // wave-uniform
-        const double ar_ = p.alpha[gr];
-        const double* kp = p.Kn + gr * p.ld + gc;
-        double sr_ = 0.0, zr_ = 0.0, gr_ = 0.0;
-        if constexpr (LAP) { sr_ = p.s[gr]; zr_ = p.z[gr]; gr_ = p.g[gr]; }
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {                            // the thread's two columns, one after the other
-            const int64_t g = gc + 64 * c;
-            const bool in = g < p.n;
-            double e2[DC];
-            double sq = 0.0;
-            if (LDS) {
-                const double* ar = &As[lr * DC];
-                const double* bc = &Bs[cp + 64 * c];
-#pragma unroll
-                for (int k = 0; k < DC; ++k) {
-                    const double e = ar[k] - bc[k * RT];
-                    e2[k] = e * e;
-                    sq += e2[k];
-                }
-            } else {
-                const double* ar = p.Z + gr * d;
-                const double* b = p.Z + (in ? g : 0) * d;
-#pragma unroll
-                for (int k = 0; k < DC; ++k) {
-                    const int kk = p.k0 + k;
-                    const double e = (kk < d) ? ar[kk] - b[kk] : 0.0;
-                    e2[k] = e * e;
-                    sq += e2[k];
-                }
-                for (int kk = 0; kk < p.k0; ++kk) {
-                    const double e = ar[kk] - b[kk];
-                    sq = fma(e, e, sq);
-                }
-                for (int kk = p.k0 + DC; kk < d; ++kk) {
-                    const double e = ar[kk] - b[kk];
-                    sq = fma(e, e, sq);
-                }
-            }
-            // Kn holds -K_y^-1, valid on and below the diagonal only
-            double w;
-            if constexpr (LAP) {
-                w = 0.0;
-                if (in && g <= gr) {
-                    w = fma(ar_, p.alpha[g], (sr_ * p.s[g]) * kp[64 * c]);
-                    w = fma(zr_, p.g[g], w);
-                    w = fma(p.z[g], gr_, w);
-                }
-                if (g != gr) w += w;
-            } else {
-                w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
-                if (g == gr) acc_n += w;
-                else w += w;
-            }
-            double wx, ws;                                       // the weight of the lengthscale sums and of sigma's
-            if constexpr (F == 0) {
-                wx = ws = w * exp(p.coef * sq);
-            } else {
-                double kk, hh;
-                matern_kh<F>(p.coef, sq, kk, hh);
-                wx = w * hh;
-                ws = w * kk;
-            }
-#pragma unroll
-            for (int k = 0; k < DC; ++k) acc[k] = fma(wx, e2[k], acc[k]);
-            acc_l = fma(wx, sq, acc_l);
-            acc_s += ws;
-        }
-    }
-    // 64 lanes by a butterfly, then the four waves in order: the same order every run
-    const int wave = tid >> 6;
-    auto wave_sum = [](double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        return v;
-    };
-#pragma unroll
-    for (int k = 0; k < DC; ++k) {
-        const double v = wave_sum(acc[k]);
-        if (cp == 0) red[wave][k] = v;
-    }
-    {
-        const double vl = wave_sum(acc_l), vs = wave_sum(acc_s), vn = wave_sum(acc_n);
-        if (cp == 0) { red[wave][DC] = vl; red[wave][DC + 1] = vs; red[wave][DC + 2] = vn; }
-    }
-    __syncthreads();
-    if (tid < DC + 3)
-        p.partial[(int64_t)tid * p.nblk + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    lower_tile_sums<ArdTerms<DC, F, LAP>, LDS>(p);
 }
 
 // out[j] = sum over the blocks of partial[j * nblk + b]: thread t adds blocks t, t + 256, ... in order, then a fixed tree
 __global__ __launch_bounds__(256) void ard_reduce_kernel(const double* partial, int64_t nblk, double* out) {
-    __shared__ double sh[256];
+    __shared__ double sh[1][256];
     const double* in = partial + (int64_t)blockIdx.x * nblk;
-    double v = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += 256) v += in[b];
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+    double v[1] = {0.0};
+    for (int64_t b = threadIdx.x; b < nblk; b += 256) v[0] += in[b];
+    block_tree256(sh, v, (int)threadIdx.x);
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0][0];
 }
 
 // ---- 11 basis sums of the CO2 composite kernel (kind 3; CO2_example.py:9-64) ----------------------------------------
-// A sibling of grad_ard_kernel: the same lower-tile enumeration over Kn = -K_y^-1, the same columns and rows per thread,
-// the same weight w = alpha_i alpha_j + Kn_ij (strictly-lower elements twice), the same reduction orders and
-// ard_reduce_kernel behind it.  Per element, with sq the squared distance and r = sqrt(sq):
+// The regression weight w = alpha_i alpha_j + Kn_ij.  Per element, with sq the squared distance and r = sqrt(sq):
 //     e1 = exp(n1 sq)   s2 = sin^2(pi r)   q2 = exp(n4 sq + n5 s2)   u = cu sq   p3 = exp(n8 log1p(u))   e4 = exp(n10 sq)
 //     S1 += w e1   S2 += w e1 sq   S3 += w q2   S4 += w q2 sq   S5 += w q2 s2
 //     S6 += w p3   S7 += w p3 sq / (1 + u)   S8 += w p3 (u / (1 + u) - log1p(u))   S9 += w e4   S10 += w e4 sq
 //     S11 += w on the diagonal
 // The six constants come from the host (regress.hip: lml_grad_co2_impl), which also turns the sums into the twelve
 // derivatives.  Every term is regular at sq == 0 (e1 = 1, s2 = 0, u = 0): nothing is selected on the diagonal or for
-// duplicate points.  LDS: d <= GRAD_MAXD, both tile edges staged as in grad_trace_kernel; beyond, X comes from global
-// memory.  Accumulators are named by compile-time constants only.
+// duplicate points.  LDS rows are d wide (d <= GRAD_MAXD).
 constexpr int CO2_NS = 11;
 
 struct Co2Dev {
@@ -366,97 +419,44 @@ struct Co2Dev {
     int64_t nblk;
 };
 
+struct Co2Terms {
+    typedef Co2Dev Dev;
+    typedef RegWeight Weight;
+    static constexpr int DC = 0, NS = CO2_NS;
+    struct Dist {
+        double sq;
+    };
+    template <bool LDS>
+    static __device__ __forceinline__ void dist(const Dev& p, const double* a, const double* b, Dist& x) {
+        x.sq = sqdist1(a, b, LDS ? RT : 1, p.d);
+    }
+    static __device__ __forceinline__ void add(const Dev& p, double w, const Dist& x, double (&acc)[NS]) {
+        const double sq = x.sq;
+        const double sn = sin(M_PI * sqrt(sq));
+        const double s2 = sn * sn;
+        const double u = p.cu * sq;
+        const double l1p = log1p(u);
+        const double rc = 1.0 / (1.0 + u);
+        const double w1 = w * exp(p.n1 * sq);
+        const double w2 = w * exp(fma(p.n4, sq, p.n5 * s2));
+        const double w3 = w * exp(p.n8 * l1p);
+        const double w4 = w * exp(p.n10 * sq);
+        acc[0] += w1;
+        acc[1] = fma(w1, sq, acc[1]);
+        acc[2] += w2;
+        acc[3] = fma(w2, sq, acc[3]);
+        acc[4] = fma(w2, s2, acc[4]);
+        acc[5] += w3;
+        acc[6] = fma(w3, sq * rc, acc[6]);
+        acc[7] = fma(w3, u * rc - l1p, acc[7]);
+        acc[8] += w4;
+        acc[9] = fma(w4, sq, acc[9]);
+    }
+};
+
 template <bool LDS>
 __global__ __launch_bounds__(256) void grad_co2_kernel(const Co2Dev p) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double red[4][CO2_NS];
-    const int s = blockIdx.x;
-    int ti = (int)((sqrtf(8.f * (float)s + 1.f) - 1.f) * 0.5f);
-    while ((ti + 1) * (ti + 2) / 2 <= s) ++ti;
-    while (ti * (ti + 1) / 2 > s) --ti;
-    const int tj = s - ti * (ti + 1) / 2;
-    const int d = p.d;
-    const int64_t grow0 = (int64_t)ti * RT, gcol0 = (int64_t)tj * RT;
-    const int tid = threadIdx.x;
-    double* As = lds;               // [RT][d]
-    double* Bs = lds + RT * d;      // [d][RT]
-    if (LDS) {
-        for (int e = tid; e < RT * d; e += 256) {
-            const int r = e / d, k = e - r * d;
-            const int64_t ga = grow0 + r, gb = gcol0 + r;
-            As[r * d + k] = (ga < p.n) ? p.Z[ga * d + k] : 0.0;
-            Bs[k * RT + r] = (gb < p.n) ? p.Z[gb * d + k] : 0.0;
-        }
-        __syncthreads();
-    }
-    const int cp = tid & 63, rg = tid >> 6;
-    const int64_t gc = gcol0 + cp;      // the thread's columns: gc and gc + 64
-    double acc[CO2_NS];
-#pragma unroll
-    for (int k = 0; k < CO2_NS; ++k) acc[k] = 0.0;
-    for (int r = 0; r < 32; ++r) {
-        const int lr = 32 * rg + r;
-        const int64_t gr = grow0 + lr;
-        if (gr >= p.n) break;                                    // wave-uniform
-        const double ar_ = p.alpha[gr];
-        const double* kp = p.Kn + gr * p.ld + gc;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int64_t g = gc + 64 * c;
-            const bool in = g < p.n;
-            double sq = 0.0;
-            if (LDS) {
-                const double* ar = &As[lr * d];
-                const double* bc = &Bs[cp + 64 * c];
-                for (int k = 0; k < d; ++k) {
-                    const double e = ar[k] - bc[k * RT];
-                    sq = fma(e, e, sq);
-                }
-            } else {
-                const double* ar = p.Z + gr * d;
-                const double* b = p.Z + (in ? g : 0) * d;
-                for (int k = 0; k < d; ++k) {
-                    const double e = ar[k] - b[k];
-                    sq = fma(e, e, sq);
-                }
-            }
-            // Kn holds -K_y^-1, valid on and below the diagonal only
-            double w = (in && g <= gr) ? fma(ar_, p.alpha[g], kp[64 * c]) : 0.0;
-            if (g == gr) acc[10] += w;
-            else w += w;
-            const double sn = sin(M_PI * sqrt(sq));
-            const double s2 = sn * sn;
-            const double u = p.cu * sq;
-            const double l1p = log1p(u);
-            const double rc = 1.0 / (1.0 + u);
-            const double w1 = w * exp(p.n1 * sq);
-            const double w2 = w * exp(fma(p.n4, sq, p.n5 * s2));
-            const double w3 = w * exp(p.n8 * l1p);
-            const double w4 = w * exp(p.n10 * sq);
-            acc[0] += w1;
-            acc[1] = fma(w1, sq, acc[1]);
-            acc[2] += w2;
-            acc[3] = fma(w2, sq, acc[3]);
-            acc[4] = fma(w2, s2, acc[4]);
-            acc[5] += w3;
-            acc[6] = fma(w3, sq * rc, acc[6]);
-            acc[7] = fma(w3, u * rc - l1p, acc[7]);
-            acc[8] += w4;
-            acc[9] = fma(w4, sq, acc[9]);
-        }
-    }
-    // 64 lanes by a butterfly, then the four waves in order: the same order every run
-    const int wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < CO2_NS; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (cp == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < CO2_NS)
-        p.partial[(int64_t)tid * p.nblk + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    lower_tile_sums<Co2Terms, LDS>(p);
 }
 
 __global__ void scale_inputs_kernel(const double* X, const double* r, int64_t total, int d, double* Z) {
@@ -475,12 +475,6 @@ __global__ void set_identity_kernel(double* V, int64_t ld, int64_t n) {
 // them in that order, the 64 lanes meet in a butterfly -- the same order every run.  They read rows and columns < n
 // only: whatever the identity padding holds contributes nothing.
 typedef double dbl2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // kappa_i = sum_{j >= i} U_ij^2: the diagonal of K_y^-1 = U U^T, U = L^-T upper triangular
 __global__ __launch_bounds__(256) void loo_kappa_kernel(const double* __restrict__ U, int64_t ld, int64_t n,
@@ -529,8 +523,8 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(double* A, int64_t ld
 }
 
 // D_ab = K_ab sq_ab = sig2 exp(coef sq_ab) sq_ab in full (dK/dl = D / l^3; a Matern family: D_ab = sig2 H(t_ab) sq_ab,
-// dK/dl = a^2 D / l, with the library exp), zero on padded rows and columns.  The tile
-// loop, the staging and the squared distance of grad_trace_kernel; exp by the K build's polynomial while every lane of
+// dK/dl = a^2 D / l, with the library exp), zero on padded rows and columns.  Every tile
+// of a square grid, the adjacent column pair; exp by the K build's polynomial while every lane of
 // the wave is inside its domain.  D_ab and D_ba are the same bits ((a - b)^2 == (b - a)^2, the same order over k).
 struct DmatDev {
     const double* Z;
@@ -550,15 +544,7 @@ __global__ __launch_bounds__(256) void loo_dmat_kernel(const DmatDev p) {
     const int tid = threadIdx.x;
     double* As = lds;               // [RT][d]
     double* Bs = lds + RT * d;      // [d][RT]
-    if (LDS) {
-        for (int e = tid; e < RT * d; e += 256) {
-            const int r = e / d, k = e - r * d;
-            const int64_t ga = grow0 + r, gb = gcol0 + r;
-            As[r * d + k] = (ga < p.n) ? p.Z[ga * d + k] : 0.0;
-            Bs[k * RT + r] = (gb < p.n) ? p.Z[gb * d + k] : 0.0;
-        }
-        __syncthreads();
-    }
+    if (LDS) stage_edges<0>(As, Bs, p.Z, p.Z, grow0, gcol0, p.n, p.n, d, tid);
     const int cp = tid & 63, rg = tid >> 6;
     const int64_t gc = gcol0 + 2 * cp;
     const bool in0 = gc < p.n, in1 = gc + 1 < p.n;
@@ -567,26 +553,8 @@ __global__ __launch_bounds__(256) void loo_dmat_kernel(const DmatDev p) {
         const int64_t gr = grow0 + lr;
         const bool inr = gr < p.n;                               // wave-uniform
         double s0 = 0.0, s1 = 0.0;
-        if (LDS) {
-            const double* ar = &As[lr * d];
-            const double* bc = &Bs[2 * cp];
-            for (int k = 0; k < d; ++k) {
-                const double a = ar[k];
-                const double e0 = a - bc[k * RT], e1 = a - bc[k * RT + 1];
-                s0 = fma(e0, e0, s0);
-                s1 = fma(e1, e1, s1);
-            }
-        } else {
-            const double* ar = p.Z + (inr ? gr : 0) * d;
-            const double* b0 = p.Z + (in0 ? gc : 0) * d;
-            const double* b1 = p.Z + (in1 ? gc + 1 : 0) * d;
-            for (int k = 0; k < d; ++k) {
-                const double a = ar[k];
-                const double e0 = a - b0[k], e1 = a - b1[k];
-                s0 = fma(e0, e0, s0);
-                s1 = fma(e1, e1, s1);
-            }
-        }
+        if (LDS) sqdist2(&As[lr * d], &Bs[2 * cp], &Bs[2 * cp + 1], RT, d, s0, s1);
+        else sqdist2(p.Z + (inr ? gr : 0) * d, p.Z + (in0 ? gc : 0) * d, p.Z + (in1 ? gc + 1 : 0) * d, 1, d, s0, s1);
         double e0, e1;
         if constexpr (F == 0) {
             const double x0 = p.coef * s0, x1 = p.coef * s1;
@@ -667,24 +635,19 @@ __global__ __launch_bounds__(256) void row_dot2_kernel(const double* __restrict_
 // block 0: l, block 1: sigma, block 2: noise (gpmi_internal.h: LooGradArgs).  Thread t adds points t, t + 256, ... in
 // order, then a fixed tree.
 __global__ __launch_bounds__(256) void loo_grad_sums_kernel(const LooGradArgs p) {
-    __shared__ double sh[256];
+    __shared__ double sh[1][256];
     const int comp = blockIdx.x;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int64_t i = threadIdx.x; i < p.n; i += 256) {
         const double a = p.alpha[i], k = p.kappa[i];
         double r, s;
         if (comp == 0) { r = -p.un[i]; s = -p.sn[i]; }
         else if (comp == 1) { r = a + p.noise * p.qn[i]; s = k - p.noise * p.cn[i]; }
         else { r = -p.qn[i]; s = p.cn[i]; }
-        acc += (a * r - .5 * (1.0 + a * a / k) * s) / k;
+        acc[0] += (a * r - .5 * (1.0 + a * a / k) * s) / k;
     }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) p.out3[comp] = sh[0];
+    block_tree256(sh, acc, (int)threadIdx.x);
+    if (threadIdx.x == 0) p.out3[comp] = sh[0][0];
 }
 
 }  // namespace
@@ -702,39 +665,39 @@ hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, 
     return hipGetLastError();
 }
 
-int64_t grad_ard_blocks(const GradArdArgs& a) {
-    const int64_t T = (a.n + RT - 1) / RT;
+// lower 128 x 128 tiles of an n x n matrix
+int64_t tri_tile_count(int64_t n) {
+    const int64_t T = (n + RT - 1) / RT;
     return T * (T + 1) / 2;
 }
 // dimensions per launch: the narrowest of 4 / 8 / 16 / 32 that holds d, 32 beyond
 int64_t grad_ard_width(const GradArdArgs& a) { return a.d <= 4 ? 4 : a.d <= 8 ? 8 : a.d <= 16 ? 16 : 32; }
 int64_t grad_ard_launches(const GradArdArgs& a) { return a.d <= GRAD_MAXD ? 1 : (a.d + GRAD_MAXD - 1) / GRAD_MAXD; }
 
-template <int DC, int F>
-static void grad_ard_go(hipStream_t s, const ArdDev& p) {
-    hipLaunchKernelGGL((grad_ard_kernel<DC, true, F>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
+// f(std::integral_constant<int, family>()): the runtime family (0 .. 3, checked by the caller) as a compile-time constant
+template <class Fn>
+static void with_family(int family, Fn&& f) {
+    switch (family) {
+        case 0: f(std::integral_constant<int, 0>()); break;
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        default: f(std::integral_constant<int, 3>()); break;
+    }
 }
 
-template <int DC>
-static void laplace_ard_go(hipStream_t s, const ArdLapDev& p) {
-    hipLaunchKernelGGL((grad_ard_kernel<DC, true, 0, true>), dim3((unsigned)p.nblk), dim3(256), (size_t)2 * RT * DC * sizeof(double), s, p);
-}
-
-static void laplace_ard_launch(hipStream_t s, const ArdLapDev& p, int64_t d, int w) {
-    if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, 0, true>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
-    else if (w == 4) laplace_ard_go<4>(s, p);
-    else if (w == 8) laplace_ard_go<8>(s, p);
-    else if (w == 16) laplace_ard_go<16>(s, p);
-    else laplace_ard_go<32>(s, p);
-}
-
-template <int F>
-static void grad_ard_launch(hipStream_t s, const ArdDev& p, int64_t d, int w) {
-    if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, F>), dim3((unsigned)p.nblk), dim3(256), 0, s, p);
-    else if (w == 4) grad_ard_go<4, F>(s, p);
-    else if (w == 8) grad_ard_go<8, F>(s, p);
-    else if (w == 16) grad_ard_go<16, F>(s, p);
-    else grad_ard_go<32, F>(s, p);
+// the width ladder of both weights: d <= 32 from LDS at width w = grad_ard_width, beyond from global memory at 32
+template <int F, bool LAP>
+static void grad_ard_launch(hipStream_t s, const typename ArdDevOf<LAP>::type& p, int64_t d, int w) {
+    const dim3 grid((unsigned)p.nblk), block(256);
+    auto go = [&](auto dc) {
+        constexpr int DC = decltype(dc)::value;
+        hipLaunchKernelGGL((grad_ard_kernel<DC, true, F, LAP>), grid, block, (size_t)2 * RT * DC * sizeof(double), s, p);
+    };
+    if (d > GRAD_MAXD) hipLaunchKernelGGL((grad_ard_kernel<32, false, F, LAP>), grid, block, 0, s, p);
+    else if (w == 4) go(std::integral_constant<int, 4>());
+    else if (w == 8) go(std::integral_constant<int, 8>());
+    else if (w == 16) go(std::integral_constant<int, 16>());
+    else go(std::integral_constant<int, 32>());
 }
 
 hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
@@ -744,19 +707,14 @@ hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
     if (lap && (a.family != 0 || !a.lap_z || !a.lap_g)) return hipErrorInvalidValue;
     ArdLapDev p;
     p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld; p.coef = a.coef;
-    p.partial = a.partial; p.nblk = grad_ard_blocks(a);
+    p.partial = a.partial; p.nblk = tri_tile_count(a.n);
     p.s = a.lap_s; p.z = a.lap_z; p.g = a.lap_g;
     const int w = (int)grad_ard_width(a);
     const int64_t nl = grad_ard_launches(a);
     for (int64_t q = 0; q < nl; ++q) {       // d > 32: every launch recomputes the whole squared distance and reads Kn again
         p.k0 = (int)(q * GRAD_MAXD);
-        if (lap) laplace_ard_launch(s, p, a.d, w);
-        else switch (a.family) {
-            case 0: grad_ard_launch<0>(s, p, a.d, w); break;
-            case 1: grad_ard_launch<1>(s, p, a.d, w); break;
-            case 2: grad_ard_launch<2>(s, p, a.d, w); break;
-            default: grad_ard_launch<3>(s, p, a.d, w); break;
-        }
+        if (lap) grad_ard_launch<0, true>(s, p, a.d, w);
+        else with_family(a.family, [&](auto f) { grad_ard_launch<decltype(f)::value, false>(s, p, a.d, w); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(ard_reduce_kernel, dim3((unsigned)(w + 3)), dim3(256), 0, s, a.partial, p.nblk, a.sums + q * (w + 3));
@@ -765,17 +723,12 @@ hipError_t launch_grad_ard(hipStream_t s, const GradArdArgs& a) {
     return hipSuccess;
 }
 
-int64_t grad_co2_blocks(const GradCo2Args& a) {
-    const int64_t T = (a.n + RT - 1) / RT;
-    return T * (T + 1) / 2;
-}
-
 hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a) {
     if (a.n <= 0 || a.d <= 0) return hipSuccess;
     Co2Dev p;
     p.Z = a.Z; p.n = a.n; p.d = (int)a.d; p.alpha = a.alpha; p.Kn = a.Kn; p.ld = a.ld;
     p.n1 = a.n1; p.n4 = a.n4; p.n5 = a.n5; p.cu = a.cu; p.n8 = a.n8; p.n10 = a.n10;
-    p.partial = a.partial; p.nblk = grad_co2_blocks(a);
+    p.partial = a.partial; p.nblk = tri_tile_count(a.n);
     const dim3 grid((unsigned)p.nblk), block(256);
     if (a.d <= GRAD_MAXD) hipLaunchKernelGGL(grad_co2_kernel<true>, grid, block, (size_t)2 * RT * a.d * sizeof(double), s, p);
     else hipLaunchKernelGGL(grad_co2_kernel<false>, grid, block, 0, s, p);
@@ -786,8 +739,7 @@ hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a) {
 }
 
 int64_t grad_trace_blocks(const GradArgs& a) {
-    const int64_t Tm = (a.nrows + RT - 1) / RT, Tn = (a.nB + RT - 1) / RT;
-    return a.tri ? Tm * (Tm + 1) / 2 : Tm * Tn;
+    return a.tri ? tri_tile_count(a.nrows) : ((a.nrows + RT - 1) / RT) * ((a.nB + RT - 1) / RT);
 }
 
 hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a) {
@@ -803,16 +755,11 @@ hipError_t launch_grad_trace(hipStream_t s, const GradArgs& a) {
     if (a.family < 0 || a.family > 3) return hipErrorInvalidValue;
     const dim3 grid((unsigned)grad_trace_blocks(a)), block(256);
     const size_t lds = (size_t)2 * RT * a.d * sizeof(double);
-#define GRAD_TRACE_FAMILY(FF)                                                                                          \
-    if (a.d <= GRAD_MAXD) hipLaunchKernelGGL((grad_trace_kernel<true, FF>), grid, block, lds, s, p);                   \
-    else hipLaunchKernelGGL((grad_trace_kernel<false, FF>), grid, block, 0, s, p)
-    switch (a.family) {
-        case 0: GRAD_TRACE_FAMILY(0); break;
-        case 1: GRAD_TRACE_FAMILY(1); break;
-        case 2: GRAD_TRACE_FAMILY(2); break;
-        default: GRAD_TRACE_FAMILY(3); break;
-    }
-#undef GRAD_TRACE_FAMILY
+    with_family(a.family, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        if (a.d <= GRAD_MAXD) hipLaunchKernelGGL((grad_trace_kernel<true, F>), grid, block, lds, s, p);
+        else hipLaunchKernelGGL((grad_trace_kernel<false, F>), grid, block, 0, s, p);
+    });
     return hipGetLastError();
 }
 
@@ -846,16 +793,12 @@ hipError_t launch_loo_dmat(hipStream_t s, const double* Z, int64_t n, int64_t d,
     DmatDev p;
     p.Z = Z; p.n = n; p.d = (int)d; p.coef = coef; p.sig2 = sig2; p.D = D; p.ld = ld;
     const unsigned T = (unsigned)(np / RT);
-#define LOO_DMAT_FAMILY(FF)                                                                                            \
-    if (d <= GRAD_MAXD) hipLaunchKernelGGL((loo_dmat_kernel<true, FF>), dim3(T, T), dim3(256), (size_t)2 * RT * d * sizeof(double), s, p); \
-    else hipLaunchKernelGGL((loo_dmat_kernel<false, FF>), dim3(T, T), dim3(256), 0, s, p)
-    switch (family) {
-        case 0: LOO_DMAT_FAMILY(0); break;
-        case 1: LOO_DMAT_FAMILY(1); break;
-        case 2: LOO_DMAT_FAMILY(2); break;
-        default: LOO_DMAT_FAMILY(3); break;
-    }
-#undef LOO_DMAT_FAMILY
+    const dim3 grid(T, T), block(256);
+    with_family(family, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        if (d <= GRAD_MAXD) hipLaunchKernelGGL((loo_dmat_kernel<true, F>), grid, block, (size_t)2 * RT * d * sizeof(double), s, p);
+        else hipLaunchKernelGGL((loo_dmat_kernel<false, F>), grid, block, 0, s, p);
+    });
     return hipGetLastError();
 }
 

@@ -57,21 +57,30 @@ static int solve_epilogue(gpmi_ctx* c, const char* api) {
     return gave_up ? fail_gave_up(api) : GPMI_OK;
 }
 
-int grad_ard_finish(gpmi_ctx* c, GradArdArgs& a, size_t span, const char* solve_api, std::vector<double>* sums) {
+// The ending of a lower-tile sums kernel (grad.hip: the ARD and the CO2 sums): the partials' and the sums' buffers, the
+// launch, the end of the caller's span, the ncomp x launches sums to the host and the solve epilogue (solve_api null: a
+// plain synchronisation)
+template <class Args>
+static int tile_sums_finish(gpmi_ctx* c, Args& a, hipError_t (*launch)(hipStream_t, const Args&), int64_t ncomp,
+                            int64_t launches, size_t span, const char* solve_api, double* sums) {
     hipStream_t s = c->stream;
-    const int64_t nblk = grad_ard_blocks(a), nl = grad_ard_launches(a), w = grad_ard_width(a);
-    HIP_TRY(c->gpart.ensure((size_t)nblk * (size_t)(w + 3) * 8));
-    HIP_TRY(c->gsum.ensure((size_t)nl * (size_t)(w + 3) * 8));
+    HIP_TRY(c->gpart.ensure((size_t)tri_tile_count(a.n) * (size_t)ncomp * 8));
+    HIP_TRY(c->gsum.ensure((size_t)launches * (size_t)ncomp * 8));
     a.partial = c->gpart.as<double>();
     a.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_ard(s, a));
+    HIP_TRY(launch(s, a));
     c->span_end(span);
-    sums->resize((size_t)nl * (size_t)(w + 3));
-    HIP_TRY(hipMemcpyAsync(sums->data(), a.sums, sums->size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sums, a.sums, (size_t)launches * (size_t)ncomp * 8, hipMemcpyDeviceToHost, s));
     if (solve_api) return solve_epilogue(c, solve_api);
     HIP_TRY(hipStreamSynchronize(s));
     c->timers_collect();
     return GPMI_OK;
+}
+
+int grad_ard_finish(gpmi_ctx* c, GradArdArgs& a, size_t span, const char* solve_api, std::vector<double>* sums) {
+    const int64_t nl = grad_ard_launches(a), ncomp = grad_ard_width(a) + 3;
+    sums->resize((size_t)nl * (size_t)ncomp);
+    return tile_sums_finish(c, a, launch_grad_ard, ncomp, nl, span, solve_api, sums->data());
 }
 
 // launch q holds sum w K/sigma^2 e_k^2 for its dimensions, then (first launch) the l, sigma and noise sums
@@ -235,7 +244,6 @@ int lml_grad_co2_impl(gpmi_ctx* c, double* d_theta, double* d_noise) {
     int rc = grad_front(c, "gpmi_lml_grad_co2: no regression factorisation resident (call gpmi_factorize)",
                         nullptr /* the kind is checked above */, GPMI_T_GRAD, true, &alpha, &sp);
     if (rc) return rc;
-    hipStream_t s = c->stream;
     const double* th = c->kpv;             // th[i] = theta_(i+1)
     GradCo2Args a;
     a.Z = c->x_train(); a.n = c->N; a.d = c->d;
@@ -246,15 +254,8 @@ int lml_grad_co2_impl(gpmi_ctx* c, double* d_theta, double* d_noise) {
     a.cu = 1.0 / (2.0 * th[7] * (th[6] * th[6]));
     a.n8 = -th[7];
     a.n10 = -1.0 / (2.0 * th[9] * th[9]);
-    HIP_TRY(c->gpart.ensure((size_t)grad_co2_blocks(a) * 11 * 8));
-    HIP_TRY(c->gsum.ensure(11 * 8));
-    a.partial = c->gpart.as<double>();
-    a.sums = c->gsum.as<double>();
-    HIP_TRY(launch_grad_co2(s, a));
-    c->span_end(sp);
     double S[11];
-    HIP_TRY(hipMemcpyAsync(S, a.sums, sizeof S, hipMemcpyDeviceToHost, s));
-    if ((rc = solve_epilogue(c, "gpmi_lml_grad_co2"))) return rc;
+    if ((rc = tile_sums_finish(c, a, launch_grad_co2, 11, 1, sp, "gpmi_lml_grad_co2", S))) return rc;
     if (d_theta) {
         d_theta[0] = th[0] * S[0];
         d_theta[1] = .5 * (th[0] * th[0]) * S[1] / (th[1] * th[1] * th[1]);
