@@ -184,6 +184,25 @@ def append_observations(X_new, y_new, *, ctx=None):
     return ctx.append(X_new, y_new)
 
 
+def remove_observations(idx, *, ctx=None):
+    """Take the observations at the 0-based positions idx (distinct, any order) out of the regression fit resident in ctx
+    without refitting: O(N^2 k) instead of O(N^3).  The surviving points keep their relative order.  Returns the
+    log-marginal-likelihood of the surviving points; predictions, gradients, leave-one-out calls and append_observations
+    then see the reduced fit."""
+    ctx = ctx or default_context()
+    return ctx.remove(idx)
+
+
+def slide_window(X_new, y_new, *, ctx=None):
+    """One step of a sliding window over a stream: the len(y_new) oldest observations leave the fit resident in ctx and
+    the new ones enter it, both without refitting.  Returns the log-marginal-likelihood after the append.  With the
+    context options "reserve" >= len(y_new) and "remove_keep_spare" 1 no step after the first allocates."""
+    ctx = ctx or default_context()
+    k = int(np.asarray(y_new).reshape(-1).shape[0])
+    ctx.remove(np.arange(k))
+    return ctx.append(X_new, y_new)
+
+
 def f_prior(X_test, mu_prior, kernel_choice, kernel_parameter, num_fun, *, ctx=None):
     """GP prior samples, reference GP_regression.py:71-92 (s = 0.0005, sigma = 1).  With a Matern kernel_choice the
     parameter is l, a scalar or a d-vector."""

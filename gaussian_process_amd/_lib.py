@@ -51,6 +51,7 @@ SIGNATURES = {
     "gpmi_factorize": [_vp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64)],
     "gpmi_fit": [_vp, _dp, _i64, _i64, _dp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64)],
     "gpmi_append": [_vp, _dp, _i64, _dp, _dp, C.POINTER(_i64)],
+    "gpmi_remove": [_vp, C.POINTER(_i64), _i64, _dp],
     "gpmi_get_layout": [_vp, C.POINTER(_i64)],
     "gpmi_get_alpha": [_vp, _dp],
     "gpmi_get_m": [_vp, _dp],

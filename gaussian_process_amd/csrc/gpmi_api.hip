@@ -96,7 +96,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->app, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->app, &c->spareA, &c->rem, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
                        &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred,
                        &c->sp_g0, &c->sp_g1, &c->sp_g2, &c->sp_gE, &c->sp_gpart, &c->sp_gvec})
         b->release();
@@ -179,6 +179,13 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "append_skinny")) {
         if (value < -1 || value > 1) return fail_arg("append_skinny must be -1 (by size), 0 (never) or 1 (whenever allowed)");
         c->append_skinny = (int)value;
+    } else if (!strcmp(name, "remove_keep_spare")) {
+        // 0 frees the buffer a removal leaves behind (and one kept earlier); 1 keeps it for the next removal
+        c->remove_keep_spare = value ? 1 : 0;
+        if (!c->remove_keep_spare) {
+            HIP_TRY(hipSetDevice(c->device));
+            c->spareA.release();
+        }
     } else if (!strcmp(name, "lanes")) {
         if (value < 0 || value > 8) return fail_arg("lanes must be 0 (by size) .. 8");
         c->lanes = (int)value;
@@ -381,6 +388,16 @@ int gpmi_append(gpmi_ctx* c, const double* Xnew, int64_t k, const double* ynew, 
     const Tuning tn = resident_tuning(c);
     TuneScope tune_scope(&tn);
     return append_impl(c, Xnew, k, ynew, lml, bad_pivot);
+}
+
+// k observations out of the resident regression factorisation: a positive rank-k update of the trailing factor, not a
+// new fit (remove.hip).  No element of K is evaluated, so every covariance kind is served.
+int gpmi_remove(gpmi_ctx* c, const int64_t* idx, int64_t k, double* lml) {
+    if (!c) return fail_arg("gpmi_remove: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    return remove_impl(c, idx, k, lml);
 }
 
 int gpmi_get_layout(gpmi_ctx* c, int64_t* out5) {

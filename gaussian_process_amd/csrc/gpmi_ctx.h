@@ -184,6 +184,10 @@ struct gpmi_ctx {
     double sigma = 1.0, ell = 1.0;   // hyper-parameters of the resident factorisation
     double noise = 0.0;              // ... and its noise variance (regression factorisations only)
     DevBuf app;              // gpmi_append, skinny route: the new points (aligned copy) and their 128 x N0 rows of K
+    // gpmi_remove (remove.hip): the buffer a removal leaves behind, kept as the target of the next one under option
+    // "remove_keep_spare" (any fit drops it); the sweep's workspace (side vectors, rotations, the gather map)
+    int remove_keep_spare = 0;
+    DevBuf spareA, rem;
     DevBuf loov, loow;       // gpmi_loo / gpmi_loo_grad: the per-point vectors; the NB x ld row block of K_y^-1 D
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
@@ -294,6 +298,8 @@ RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld);      // K(X*
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows = 0, bool test_cols = false);
 // append.hip: k more observations into the resident regression factorisation (include/gpmi.h: gpmi_append)
 int append_impl(gpmi_ctx* c, const double* Xnew, int64_t k, const double* ynew, double* lml, int64_t* bad_pivot);
+// remove.hip: k observations out of the resident regression factorisation (include/gpmi.h: gpmi_remove)
+int remove_impl(gpmi_ctx* c, const int64_t* idx, int64_t k, double* lml);
 // with_test: the test set's rows K(X*, X) ride below the y rows (they come out as v^T = K_s^T L^-T, a7 inside a3) and
 // mean / variance (a6, a8) are read off them behind the LML
 // with_post (needs with_test): the test rows also get their own columns K_ss + jitter I, i.e. ONE Cholesky of

@@ -63,6 +63,10 @@ struct Resident {
     // next backward solve inverts again; v belongs to the shorter factor and goes, and the riding posterior factor with
     // it (one cached in P is tied to its v by v_gen: the next v_computed() outdates it)
     void factor_extended(int fused) { factor_replaced(fused); drop_v(); post_in_A = false; }
+    // gpmi_remove: the regression factor lost rows and columns and everything behind them was rotated.  The fit stays;
+    // the diagonal blocks from the first removed index on are new, so the next backward solve inverts again; v belongs to
+    // the longer factor and goes, and the riding posterior factor with it (one cached in P: as above)
+    void factor_shrunk(int fused) { factor_replaced(fused); drop_v(); post_in_A = false; }
     void block_inverses_made(bool side) { have_vinv = true; have_vside = side; }
     void fit_done(Fit f) { fit = f; }
     void drop_v() { have_v = v_in_A = false; }                             // a prediction is about to overwrite V

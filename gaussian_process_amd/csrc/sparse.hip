@@ -433,6 +433,7 @@ int sparse_fit_impl(gpmi_ctx* c, const double* Z, int64_t m, double sigma, doubl
     const SparseSlabs slabs = sparse_slabs(N, c->sparse_slab, mp);      // gpmi_sparse_plan.h
     const int64_t S = slabs.S;
     c->res.drop_fit();
+    c->spareA.release();               // any fit drops the buffer a removal kept
     c->timers_reset({GPMI_T_SPARSE, GPMI_T_KS, GPMI_T_SOLVE_V, GPMI_T_MEANVAR, GPMI_T_POSTCHOL, GPMI_T_CHOL});
     c->sig2 = sigma * sigma;
     c->coef = -.5 * (1 / (ell * ell));

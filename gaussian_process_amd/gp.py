@@ -269,6 +269,22 @@ class GPContext:
         check(st, bad.value)
         return lml.value
 
+    def remove(self, idx):
+        """the observations at the 0-based positions idx (distinct, any order; a single position may come as an int) out
+        of the resident regression fit in O(N^2 k): afterwards the context is what fit() on the surviving points, in
+        their order, with the same hyper-parameters would have left.  No element of K is evaluated, so every kernel is
+        served.  Returns the log-marginal-likelihood of the surviving points."""
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1))
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("idx must hold integers, got dtype %s" % idx.dtype)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        lml = C.c_double()
+        st = self._lib.gpmi_remove(self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.shape[0], C.byref(lml))
+        if st != _lib.GPMI_ERR_BAD_ARG:
+            self.N = self.layout()["N"]        # refused: nothing changed; otherwise the context says what is resident
+        check(st)
+        return lml.value
+
     def layout(self):
         """{N, Np, ld, rows, route} of the resident training set and factor: whether an append stayed in place shows in
         ld and rows; route is the last append's (1 skinny, 0 padded, -1 none yet)"""

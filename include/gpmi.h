@@ -88,7 +88,10 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
  *               "trsm_wave" (0/1), "rbf_blocks" (persistent blocks of the K build);
  *               gpmi_append: "reserve" (default 0: from the next fit on A is sized for N + reserve points, so that appends
  *               up to that size stay in place; setting it drops nothing), "append_skinny" (k <= 16 on a fused factor:
- *               -1 by size -- the default --, 0 the padded 128-row sweep, 1 the <= 16-row sweep kernel whenever allowed).
+ *               -1 by size -- the default --, 0 the padded 128-row sweep, 1 the <= 16-row sweep kernel whenever allowed);
+ *               gpmi_remove: "remove_keep_spare" (default 0: the buffer a removal leaves behind is freed; 1: it is kept
+ *               as the target of the next removal, so a remove / append cycle allocates nothing; any fit drops it, and
+ *               so does setting the option back to 0).
  * The context-free gpmi_dev_* primitives run with the defaults. */
 int gpmi_set_option(gpmi_ctx* ctx, const char* name, int64_t value);
 
@@ -168,6 +171,32 @@ int gpmi_fit(gpmi_ctx* ctx, const double* X, int64_t N, int64_t d, const double*
  * Timers: GPMI_T_KS the row builds, GPMI_T_SOLVE_V the sweep, GPMI_T_CHOL the border update and factorisation,
  * GPMI_T_LML.  lml / bad_pivot may be NULL. */
 int gpmi_append(gpmi_ctx* ctx, const double* Xnew, int64_t k, const double* ynew, double* lml, int64_t* bad_pivot);
+/* The k observations at the distinct 0-based positions idx (any order) of the resident ordering out of the resident
+ * REGRESSION factorisation, in O(N^2 k): afterwards the context is what gpmi_fit on the surviving points, in their
+ * relative order, with the resident kernel, lengthscales, sigma, ell and noise_var would have left -- N - k points, L,
+ * m = L^-1 y, and in *lml the LML of the N - k points -- to rounding.  With J0 = floor(min(idx) / 128) 128 the leading
+ * J0 x J0 block of the factor is the resident one bit for bit.  Every consumer of a regression fit works on the result
+ * unchanged (gpmi_append included); v of a resident test set is dropped (gpmi_predict_resident recomputes it; gpmi_post_*
+ * ask for that first).  No element of K is evaluated: every covariance kind is served, the composite kind 3 included.
+ * The rows S of L that survive satisfy L_S L_S^T = K_y[S, S]; plane rotations of the surviving columns against the
+ * removed ones, left to right, make L_S triangular again -- a POSITIVE rank-k update of the trailing factor, so no
+ * pivot can fail.  One sweep carries up to 16 removed columns; more go in descending groups of 16 (the largest first).
+ * Each sweep is one launch per 128-column block from its J0 on and one more for the y row, reads the old trailing
+ * trapezoid once and writes the new one once, out of place, into a second buffer of the resident shape (leading
+ * dimension and rows stay: a removal never shrinks the allocation; the y row moves to row ceil((N - k) / 128) 128);
+ * rows and columns below J0 move with one 2-D copy.  Afterwards the old buffer is freed, or kept for the next removal
+ * under option "remove_keep_spare".  A fused factor (option "panel_fused" 1 at fit time) gets the inverses of its new
+ * 16 x 16 diagonal tiles from tile J0 / 16 on; a first-generation factor has none and stays of its kind.  The same
+ * removal from the same fit gives the same bits every run.
+ * The training set is compacted on the device (X, y, the scaled inputs); the lanes of gpmi_lml_batch forget their copy.
+ * Refused (GPMI_ERR_BAD_ARG, nothing changed): no regression factorisation resident ("no factorisation resident"), a
+ * null idx, k < 1, k >= N, an index outside [0, N), a duplicate index.  Every allocation happens before anything of the
+ * resident fit changes: if one fails the call returns GPMI_ERR_RUNTIME with the old fit intact.  A runtime error behind
+ * the allocations (a copy, a launch) also returns GPMI_ERR_RUNTIME, but then as in gpmi_append: no fit resident, the
+ * training set the REDUCED one (gpmi_get_layout tells N), gpmi_factorize works on it.
+ * Timers: GPMI_T_SOLVE_V the sweeps, GPMI_T_CHOL the tile inverses, GPMI_T_LML; GPMI_T_KS holds what only moves (the
+ * 2-D copy, the rows' columns below J0, the new padding).  lml may be NULL. */
+int gpmi_remove(gpmi_ctx* ctx, const int64_t* idx, int64_t k, double* lml);
 /* The layout of the resident training set and factor, for tests and the rate script: out5 = {N, Np (N padded to 128),
  * the leading dimension of A, the rows A is laid out for, the route of the last gpmi_append that got as far as its sweep: 1 skinny,
  * 0 padded, -1 none yet}.  The leading dimension and the rows are 0 until a fit has sized A. */
