@@ -224,3 +224,111 @@ def f_prior(X_test, mu_prior, kernel_choice, kernel_parameter, num_fun, *, ctx=N
         if r is not None:
             ctx.set_lengthscales(None)
     return mu_prior + np.dot(B, np.random.normal(size=(num_test, num_fun)))     # :91
+
+
+def prediction_gradient(X_train, X_test, y_train, kernel_choice, l, *, sigma=SIGMA_F, noise=NOISE_VAR, ctx=None):
+    """Posterior mean and variance at the test points WITH their gradients with respect to the test inputs: what a
+    continuous maximisation of an acquisition function, a sensitivity analysis or input-uncertainty propagation needs
+    instead of 2 d central differences per point.  Beside prediction(): same fit, kernel_choice 'rbf' or a Matern
+    ('matern12', 'matern32', 'matern52'), l a scalar or a d-vector.  'lin' and 'per' raise ValueError.
+
+    :return: (mu (n,), var (n,), dmu (n, d), dvar (n, d)); the standard deviation's gradient is dvar / (2 sqrt(var)).
+    The fit stays resident in ctx WITH its kernel choice and lengthscales (suggest_next works on it); unlike prediction()
+    the call does not return the context to 'rbf' -- that would drop the fit -- unless it fails."""
+    _check_stationary(kernel_choice)
+    l, r = split_lengthscale(l)
+    ctx = ctx or default_context()
+    try:
+        sg, ll = _select_kernel(ctx, kernel_choice, l, sigma)
+        ctx.fit(X_train, y_train, sg, ll, noise, lengthscales=r)
+        return ctx.predict_grad(X_test)
+    except Exception:
+        ctx.set_kernel('rbf')
+        if r is not None:
+            ctx.set_lengthscales(None)
+        raise
+
+
+def _phi(u):
+    return np.exp(-0.5 * u * u) / np.sqrt(2.0 * np.pi)
+
+
+def _Phi(u):
+    from math import erf
+    return 0.5 * (1.0 + np.vectorize(erf, otypes=[np.float64])(u / np.sqrt(2.0)))
+
+
+def acquisition_and_gradient(choice, mu, var, dmu, dvar, y_best, *, kappa=2.0, xi=0.0):
+    """Value (n,) and gradient (n, d) of an acquisition function for MAXIMISATION from predict_grad's outputs (host code).
+    With sd = sqrt(var), dsd = dvar / (2 sd) and u = (mu - y_best - xi) / sd:
+        'UCB': mu + kappa sd                               gradient dmu + kappa dsd
+        'EI':  (mu - y_best - xi) Phi(u) + sd phi(u)       gradient Phi(u) dmu + phi(u) dsd
+        'PI':  Phi(u)                                      gradient phi(u) (dmu - u dsd) / sd
+    y_best is not used by 'UCB'."""
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    var = np.asarray(var, dtype=np.float64).reshape(-1)
+    dmu = np.asarray(dmu, dtype=np.float64).reshape(mu.shape[0], -1)
+    dvar = np.asarray(dvar, dtype=np.float64).reshape(mu.shape[0], -1)
+    sd = np.sqrt(var)
+    dsd = dvar / (2.0 * sd)[:, None]
+    if choice == 'UCB':
+        return mu + kappa * sd, dmu + kappa * dsd
+    if choice not in ('EI', 'PI'):
+        raise ValueError("choice must be 'UCB', 'EI' or 'PI', got %r" % (choice,))
+    imp = mu - float(y_best) - xi
+    u = imp / sd
+    Phi, phi = _Phi(u), _phi(u)
+    if choice == 'EI':
+        return imp * Phi + sd * phi, Phi[:, None] * dmu + phi[:, None] * dsd
+    return Phi, (phi / sd)[:, None] * (dmu - u[:, None] * dsd)
+
+
+def suggest_next(bounds, choice='EI', *, n_starts=16, steps=50, ctx=None, seed=0, y_best=None, kappa=2.0, xi=0.0):
+    """The next point to evaluate: the maximiser of an acquisition function over the box `bounds` ((d, 2): low, high) at
+    the regression fit resident in ctx, by multi-start projected gradient ASCENT with backtracking.  All starts move as
+    ONE test set per step (16 starts are one row group of the backward sweep), so a step is one predict_grad call plus
+    one per backtracking round.  y_best (for 'EI' and 'PI'): the incumbent; None takes the largest posterior mean over
+    the starting points.  Plain NumPy on the host; the starts are uniform in the box from RandomState(seed).
+
+    :return: (x_best (d,), value): the best point found and its acquisition value -- never below the best start's."""
+    ctx = ctx or default_context()
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+    lo, hi = b[:, 0], b[:, 1]
+    if not np.all(hi >= lo):
+        raise ValueError("bounds: every high must be >= its low")
+    rng = np.random.RandomState(seed)
+    X = lo + (hi - lo) * rng.uniform(size=(int(n_starts), b.shape[0]))
+
+    def evaluate(P):
+        mu, var, dmu, dvar = ctx.predict_grad(P)
+        return mu, var, dmu, dvar
+
+    mu, var, dmu, dvar = evaluate(X)
+    if y_best is None:
+        y_best = float(np.max(mu))
+    val, grad = acquisition_and_gradient(choice, mu, var, dmu, dvar, y_best, kappa=kappa, xi=xi)
+    step = np.full(X.shape[0], 0.1) * float(np.max(hi - lo) if b.shape[0] else 1.0)
+    for _ in range(int(steps)):
+        gn = np.sqrt(np.sum(grad * grad, axis=1))
+        direction = grad / np.where(gn > 0, gn, 1.0)[:, None]
+        active = np.isfinite(val) & np.all(np.isfinite(grad), axis=1) & (gn > 0)
+        moved = np.zeros(X.shape[0], dtype=bool)
+        for _bt in range(8):                          # backtracking: halve the step of every start that did not improve
+            todo = active & ~moved
+            if not np.any(todo):
+                break
+            trial = np.clip(X + step[:, None] * direction, lo, hi)
+            trial[~todo] = X[~todo]
+            tmu, tvar, tdmu, tdvar = evaluate(trial)
+            tval, tgrad = acquisition_and_gradient(choice, tmu, tvar, tdmu, tdvar, y_best, kappa=kappa, xi=xi)
+            better = todo & np.isfinite(tval) & (tval > val)
+            X[better] = trial[better]
+            val[better] = tval[better]
+            grad[better] = tgrad[better]
+            moved |= better
+            step[todo & ~better] *= 0.5
+        step[moved] *= 1.5
+        if not np.any(moved):
+            break
+    best = int(np.nanargmax(val))
+    return X[best].copy(), float(val[best])

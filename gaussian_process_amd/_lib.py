@@ -60,6 +60,7 @@ SIGNATURES = {
     "gpmi_set_test": [_vp, _dp, _i64],
     "gpmi_predict_resident": [_vp, _dp, _dp, C.c_int],
     "gpmi_predict": [_vp, _dp, _i64, _dp, _dp, C.c_int],
+    "gpmi_predict_grad_resident": [_vp, _dp, _dp, _dp, _dp],
     "gpmi_fit_predict_resident": [_vp, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64), _dp, _dp, C.c_int],
     "gpmi_fit_predict_sample_resident": [_vp, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.POINTER(_i64), _dp, _dp,
                                          C.c_int, _dp],
@@ -102,6 +103,7 @@ SIGNATURES = {
     "gpmi_dev_potrf_block": [_vp, _vp, _i64, _i64, _i64, _vp],
     "gpmi_dev_trsm_block": [_vp, _vp, _i64, _vp, _i64, _i64, _i64],
     "gpmi_dev_border_sweep": [_vp, _vp, _i64, _i64, _vp, _i64, _i64],
+    "gpmi_dev_back_sweep": [_vp, _vp, _i64, _i64, _vp, _i64, _i64],
     "gpmi_dev_gemm_nt": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int, _i64],
     "gpmi_dev_gemm_nt_rowmap": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64],
     "gpmi_dev_gemm_nt_rowmap_host": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64],

@@ -127,6 +127,19 @@ int gpmi_dev_border_sweep(void* stream, const double* L_dev, int64_t ldl, int64_
     return GPMI_OK;
 }
 
+int gpmi_dev_back_sweep(void* stream, const double* L_dev, int64_t ldl, int64_t ncols, double* X_dev, int64_t ldx,
+                        int64_t rows) {
+    if (!L_dev || !X_dev) return fail_arg("gpmi_dev_back_sweep: null pointer");
+    if (rows < 1 || rows > 16 * (int64_t)65535) return fail_arg("gpmi_dev_back_sweep: rows must be in 1..16 * 65535");
+    if (ncols < 0 || ncols % TILE) return fail_arg("gpmi_dev_back_sweep: ncols must be a multiple of 128");
+    if (ldl % 2 || ldx % 2 || ldl < ncols || ldx < ncols)
+        return fail_arg("gpmi_dev_back_sweep: ldl and ldx must be even and at least ncols");
+    if ((reinterpret_cast<uintptr_t>(L_dev) & 15) || (reinterpret_cast<uintptr_t>(X_dev) & 15))
+        return fail_arg("gpmi_dev_back_sweep: both pointers must be 16-byte aligned");
+    HIP_TRY(launch_back_sweep((hipStream_t)stream, L_dev, ldl, ncols, X_dev, ldx, rows));
+    return GPMI_OK;
+}
+
 int gpmi_dev_gemm_nt(void* stream, double* C_dev, int64_t ldc, const double* A_dev, int64_t lda,
                      const double* B_dev, int64_t ldb, int64_t M, int64_t N, int64_t K, int lower,
                      int64_t diag_off) {

@@ -200,6 +200,7 @@ RbfArgs rbf_test_train(const gpmi_ctx* c, double* out, int64_t ld) {
 
 int ensure_train_buffers(gpmi_ctx* c, int64_t test_rows, bool test_cols) {
     c->spareA.release();               // any fit into A drops the buffer a removal kept
+    c->pgW.release();                  // ... and the W of gpmi_predict_grad_resident
     c->Np = round_up(c->N, TILE);
     // option "reserve": columns and rows for that many more points, which gpmi_append then fills in place (0: cap == Np)
     const int64_t cap = round_up(c->N + c->reserve, TILE);

@@ -1,5 +1,5 @@
 // C-ABI of libgpmi355x.so (see include/gpmi.h): context lifetime, options, uploads, the covariance calls, the getters,
-// the batch of LML evaluations, and the shims in front of the models' *_impl functions (driver.hip, regress.hip,
+// the batch of LML evaluations, and the shims in front of the models' *_impl functions (driver.hip, regress.hip, predgrad.hip,
 // laplace.hip, softmax.hip, sparse.hip) that keep the reference's call surface (GP_regression.py:109-156,
 // tune_hyperparms_regression.py:292-313) reachable through plain C.
 //
@@ -96,7 +96,7 @@ int gpmi_ctx_destroy(gpmi_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->X, &c->y, &c->A, &c->info, &c->red, &c->Xs, &c->V, &c->P, &c->vec, &c->dense,
                        &c->U, &c->Kn, &c->gpart, &c->cov_a, &c->cov_b, &c->cov_out, &c->flag, &c->vside,
-                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->app, &c->spareA, &c->rem, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow,
+                       &c->Xz, &c->Xsz, &c->ard_rdev, &c->gsum, &c->app, &c->spareA, &c->rem, &c->lap, &c->lap_part, &c->lap_out, &c->sm, &c->sm_part, &c->sm_E, &c->sm_B, &c->sm_out, &c->loov, &c->loow, &c->pgW, &c->pgpart, &c->pgsum,
                        &c->sp_Zraw, &c->sp_Z, &c->sp_L, &c->sp_B, &c->sp_W, &c->sp_q, &c->sp_vec, &c->sp_part, &c->sp_scr, &c->sp_info, &c->sp_pred,
                        &c->sp_g0, &c->sp_g1, &c->sp_g2, &c->sp_gE, &c->sp_gpart, &c->sp_gvec})
         b->release();
@@ -179,6 +179,12 @@ int gpmi_set_option(gpmi_ctx* c, const char* name, int64_t value) {
     } else if (!strcmp(name, "append_skinny")) {
         if (value < -1 || value > 1) return fail_arg("append_skinny must be -1 (by size), 0 (never) or 1 (whenever allowed)");
         c->append_skinny = (int)value;
+    } else if (!strcmp(name, "pgrad_sweep")) {
+        if (value < -1 || value > 1) return fail_arg("pgrad_sweep must be -1 (by size), 0 (the inverse route) or 1 (the sweep route whenever allowed)");
+        c->pgrad_sweep = (int)value;
+    } else if (!strcmp(name, "pgrad_sweep_max")) {
+        if (value < 0) return fail_arg("pgrad_sweep_max must be >= 0");
+        c->pgrad_sweep_max = value;
     } else if (!strcmp(name, "remove_keep_spare")) {
         // 0 frees the buffer a removal leaves behind (and one kept earlier); 1 keeps it for the next removal
         c->remove_keep_spare = value ? 1 : 0;
@@ -514,6 +520,15 @@ int gpmi_predict(gpmi_ctx* c, const double* Xs, int64_t n, double* mu, double* o
     int rc = gpmi_set_test(c, Xs, n);
     if (rc) return rc;
     return gpmi_predict_resident(c, mu, out2, want_sd);
+}
+
+// the gradients of the prediction at the resident test inputs (predgrad.hip); solves with the resident factor's kind of leaves
+int gpmi_predict_grad_resident(gpmi_ctx* c, double* mu, double* var, double* dmu, double* dvar) {
+    if (!c) return fail_arg("gpmi_predict_grad: null context");
+    HIP_TRY(hipSetDevice(c->device));
+    const Tuning tn = resident_tuning(c);
+    TuneScope tune_scope(&tn);
+    return predict_grad_impl(c, mu, var, dmu, dvar);
 }
 
 // Regression behind its fit (regress.hip): the gradient and leave-one-out calls solve with the kind of leaves that produced

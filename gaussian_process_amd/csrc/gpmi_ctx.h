@@ -14,6 +14,7 @@
 
 #include "../../include/gpmi.h"
 #include "gpmi_internal.h"
+#include "gpmi_pgrad_plan.h"
 #include "gpmi_state.h"
 
 namespace gpmi {
@@ -188,6 +189,11 @@ struct gpmi_ctx {
     // "remove_keep_spare" (any fit drops it); the sweep's workspace (side vectors, rotations, the gather map)
     int remove_keep_spare = 0;
     DevBuf spareA, rem;
+    // gpmi_predict_grad_resident (predgrad.hip): W = V L^-1 (n_p x (Np + ld_pad), grown on demand, released by the next
+    // fit into A), the per-chunk partial sums and the sums
+    int pgrad_sweep = -1;                // option "pgrad_sweep": -1 by size, 0 the inverse route, 1 the sweep route whenever allowed
+    int64_t pgrad_sweep_max = gpmi::PGRAD_SWEEP_MAX_DEFAULT;   // option "pgrad_sweep_max" (gpmi_pgrad_plan.h: PGRAD_SWEEP_MAX_DEFAULT, measured)
+    DevBuf pgW, pgpart, pgsum;
     DevBuf loov, loow;       // gpmi_loo / gpmi_loo_grad: the per-point vectors; the NB x ld row block of K_y^-1 D
     // binary classification (laplace.hip): A holds the factor of B = I + W^1/2 K W^1/2 at the mode f^, lap holds f^,
     // grad log p(y|f^) and W^1/2 (with the Newton iterates), lap_part the tile partials of the matrix-vector products.
@@ -319,6 +325,11 @@ hipError_t backward_solve_resident(gpmi_ctx* c, double* x2, double** x_out);
 // the same for a right-hand side the caller has put into x2[0 .. Np) (zero past N), which leaves the y row alone
 hipError_t backward_solve_rhs(gpmi_ctx* c, double* x2, double** x_out);
 int fail_gave_up(const char* api);
+// The end of a call that ran a backward solve, behind the caller's own device-to-host copies: the read of the one-launch
+// solve's give-up word where that solve ran, the call's one synchronisation, the timers, the word's status under `api`
+int solve_epilogue(gpmi_ctx* c, const char* api);
+// predgrad.hip: the gradients of the predictive mean and variance at the resident test inputs
+int predict_grad_impl(gpmi_ctx* c, double* mu, double* var, double* dmu, double* dvar);
 // regress.hip: the regression calls of include/gpmi.h on the resident factorisation, behind the shims' pointer checks
 int alpha_impl(gpmi_ctx* c, double* alpha_out);
 // The body of the regression gradients' front, for any factor resident in A: the slot's timer reset, U, (want_kn) Kn and

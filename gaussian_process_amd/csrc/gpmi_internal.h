@@ -138,6 +138,11 @@ hipError_t launch_trsm128(hipStream_t s, const double* L, int64_t ldl, double* X
 // read nor written; of L it reads what trsm128 reads, block by block.
 hipError_t launch_border_sweep(hipStream_t s, const double* L, int64_t ldl, int64_t ncols, double* X, int64_t ldx,
                                int64_t rows);
+// X (rows, ncols) <- X * L^-1 for the same kind of factor (row i becomes L^-T x_i): the backward sweep, one launch per 128
+// columns from the last block to the first whatever `rows` is (16-row groups ride in a second grid dimension), L streamed
+// once per row group.  It reads and leaves alone what launch_border_sweep does.
+hipError_t launch_back_sweep(hipStream_t s, const double* L, int64_t ldl, int64_t ncols, double* X, int64_t ldx,
+                             int64_t rows);
 
 // ---- rbf.hip ---------------------------------------------------------------
 struct RbfArgs {
@@ -241,6 +246,25 @@ struct GradCo2Args {
     double* sums;             // 11 doubles
 };
 hipError_t launch_grad_co2(hipStream_t s, const GradCo2Args& a);
+// The gradients of the predictive mean and variance at the test inputs (gpmi_predict_grad_resident), without their
+// factors: with e_k = z*_ik - z_jk and g_ij = exp(coef sq_ij) (a Matern family: H(t_ij), 0 where sq_ij == 0 for nu = 1/2)
+//   sums[i * ncomp + k]     = sum_j alpha_j g_ij e_k                     k < d
+//   sums[i * ncomp + d + k] = sum_j W_ij g_ij e_k                        (W not null; ncomp = 2 d, else d)
+// One fused pass, K(X*, X) never stored, W read once, d <= 32; per-(row, column chunk) partials, added in chunk order.
+struct PgradArgs {
+    const double* Zs;         // scaled test inputs n x d (device)
+    const double* Z;          // scaled training inputs N x d
+    int64_t n, N, d;
+    const double* alpha;      // length N
+    const double* W;          // n x ldw, or null: the mean's sums only
+    int64_t ldw;
+    double coef;              // -1 / (2 l^2); family > 0: -a
+    int family = 0;
+    double* partial;          // pgrad_chunks(N) * n * ncomp doubles
+    double* sums;             // n * ncomp doubles
+};
+int64_t pgrad_chunks(int64_t N);
+hipError_t launch_pgrad(hipStream_t s, const PgradArgs& a);
 // Z[i][k] = X[i][k] / r[k]: one IEEE division per element
 hipError_t launch_scale_inputs(hipStream_t s, const double* X, const double* r, int64_t n, int64_t d, double* Z);
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n);

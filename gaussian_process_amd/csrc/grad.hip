@@ -19,6 +19,8 @@
 //   wave_sum64, block_tree256, block_partials   the reductions, each in ONE fixed order: results are bitwise reproducible
 //   lower_tile_sums           the body of the weighted sums over the lower tiles of Kn = -K_y^-1 (ARD, Laplace, CO2)
 // A kernel's own comment says only what is particular to it: its weight, its terms, its column layout.
+// pgrad_kernel (the gradients of the prediction at the test inputs) is no tile kernel: test rows against chunks of training
+// columns, the kernel element from both input sets, the same families, wave_sum64 and a fixed-order sum over the chunks.
 //
 // The per-element function is a compile-time family F (cov_family: 0 squared exponential, 1 / 2 / 3 Matern nu = 1/2,
 // 3/2, 5/2).  For a Matern, with t = a sqrt(sq), a = -coef:
@@ -650,6 +652,104 @@ __global__ __launch_bounds__(256) void loo_grad_sums_kernel(const LooGradArgs p)
     if (threadIdx.x == 0) p.out3[comp] = sh[0][0];
 }
 
+// ---- gradients of the predictive mean and variance at the test inputs --------------------------------------------------
+// Per pair (test row i, training column j): e_k = z*_ik - z_jk, sq = sum_k e_k^2 (FMA over k ascending), g = exp(coef sq)
+// (a Matern family: g = H(t), selected to 0 at sq == 0 for nu = 1/2 by matern_kh) once, then for the row's d dimensions
+//     am_k += alpha_j g e_k        and, HW:   aw_k += W_ij g e_k
+// K(X*, X) is never stored; W is read once.  A block takes RB test rows (RB * DC <= 32: a row's 2 DC sums stay in
+// registers) against PG_CHUNK training columns, a thread four of them 256 apart, so that a training point's coordinates
+// are loaded once for the RB rows.  The sums of a (row, chunk) go to the workspace -- 64 lanes by the butterfly, then the
+// four waves in order -- and launch_sum_fixed adds the chunks in index order: no atomics, the same bits every run.
+constexpr int PG_CHUNK = 1024;
+struct PgradDev {
+    const double* Zs;       // scaled test inputs n x d
+    const double* Z;        // scaled training inputs N x d
+    int64_t n, N;
+    int d;
+    const double* alpha;    // length N
+    const double* W;        // n x ldw (HW only)
+    int64_t ldw;
+    double coef;
+    double* partial;        // [chunk][row][ncomp]
+    int ncomp;              // d, or 2 d with W
+};
+
+template <int F, int DC, int RB, bool HW>
+__global__ __launch_bounds__(256) void pgrad_kernel(const PgradDev p) {
+    constexpr int NC = HW ? 2 * DC : DC;
+    __shared__ double zs[RB][DC];
+    __shared__ double red[4][RB * NC];
+    const int tid = threadIdx.x, d = p.d;
+    const int64_t i0 = (int64_t)blockIdx.x * RB;
+    if (tid < RB * DC) {
+        const int r = tid / DC, k = tid - r * DC;
+        const int64_t i = (i0 + r < p.n) ? i0 + r : p.n - 1;
+        zs[r][k] = (k < d) ? p.Zs[i * d + k] : 0.0;
+    }
+    __syncthreads();
+    double am[RB][DC], aw[HW ? RB : 1][DC];
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int k = 0; k < DC; ++k) {
+            am[r][k] = 0.0;
+            if constexpr (HW) aw[r][k] = 0.0;
+        }
+    for (int q = 0; q < PG_CHUNK / 256; ++q) {
+        const int64_t j = (int64_t)blockIdx.y * PG_CHUNK + q * 256 + tid;
+        if (j >= p.N) continue;
+        double z[DC];
+#pragma unroll
+        for (int k = 0; k < DC; ++k) z[k] = (k < d) ? p.Z[j * d + k] : 0.0;
+        const double aj = p.alpha[j];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const int64_t i = (i0 + r < p.n) ? i0 + r : p.n - 1;
+            double e[DC], sq = 0.0;
+#pragma unroll
+            for (int k = 0; k < DC; ++k) {
+                e[k] = zs[r][k] - z[k];
+                sq = fma(e[k], e[k], sq);
+            }
+            double g;
+            if constexpr (F == 0) {
+                g = exp(p.coef * sq);
+            } else {
+                double kk;
+                matern_kh<F>(p.coef, sq, kk, g);
+            }
+            const double ga = aj * g;
+#pragma unroll
+            for (int k = 0; k < DC; ++k) am[r][k] = fma(ga, e[k], am[r][k]);
+            if constexpr (HW) {
+                const double gw = p.W[i * p.ldw + j] * g;
+#pragma unroll
+                for (int k = 0; k < DC; ++k) aw[r][k] = fma(gw, e[k], aw[r][k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int k = 0; k < DC; ++k) {
+            const double v = wave_sum64(am[r][k]);
+            if ((tid & 63) == 0) red[tid >> 6][r * NC + k] = v;
+            if constexpr (HW) {
+                const double u = wave_sum64(aw[r][k]);
+                if ((tid & 63) == 0) red[tid >> 6][r * NC + DC + k] = u;
+            }
+        }
+    __syncthreads();
+    if (tid < RB * NC) {
+        const int r = tid / NC, cq = tid - r * NC;
+        const int half = cq / DC, k = cq - half * DC;
+        const int64_t i = i0 + r;
+        if (i < p.n && k < d)
+            p.partial[((int64_t)blockIdx.y * p.n + i) * p.ncomp + half * d + k] =
+                ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_set_identity_diag(hipStream_t s, double* V, int64_t ld, int64_t n) {
@@ -822,6 +922,35 @@ hipError_t launch_loo_grad_sums(hipStream_t s, const LooGradArgs& a) {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(loo_grad_sums_kernel, dim3(3), dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+int64_t pgrad_chunks(int64_t N) { return (N + PG_CHUNK - 1) / PG_CHUNK; }
+
+hipError_t launch_pgrad(hipStream_t s, const PgradArgs& a) {
+    if (a.n <= 0 || a.N <= 0) return hipSuccess;
+    if (a.d <= 0 || a.d > GRAD_MAXD || a.family < 0 || a.family > 3) return hipErrorInvalidValue;
+    PgradDev p;
+    p.Zs = a.Zs; p.Z = a.Z; p.n = a.n; p.N = a.N; p.d = (int)a.d; p.alpha = a.alpha; p.W = a.W; p.ldw = a.ldw;
+    p.coef = a.coef; p.partial = a.partial; p.ncomp = (int)(a.W ? 2 * a.d : a.d);
+    const int64_t nch = pgrad_chunks(a.N);
+    auto go = [&](auto f, auto dc, auto rb) {
+        constexpr int F = decltype(f)::value, DC = decltype(dc)::value, RB = decltype(rb)::value;
+        const dim3 grid((unsigned)((a.n + RB - 1) / RB), (unsigned)nch), block(256);      // chunks <= 65535: N < 2^26
+        if (a.W) hipLaunchKernelGGL((pgrad_kernel<F, DC, RB, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((pgrad_kernel<F, DC, RB, false>), grid, block, 0, s, p);
+    };
+    using std::integral_constant;
+    if (nch > 65535) return hipErrorInvalidValue;
+    with_family(a.family, [&](auto f) {
+        if (a.d <= 4) go(f, integral_constant<int, 4>(), integral_constant<int, 4>());
+        else if (a.d <= 8) go(f, integral_constant<int, 8>(), integral_constant<int, 4>());
+        else if (a.d <= 16) go(f, integral_constant<int, 16>(), integral_constant<int, 2>());
+        else go(f, integral_constant<int, 32>(), integral_constant<int, 1>());
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t len = a.n * p.ncomp;
+    return launch_sum_fixed(s, a.partial, nch, len, len, nullptr, 1.0, a.sums);
 }
 
 }  // namespace gpmi

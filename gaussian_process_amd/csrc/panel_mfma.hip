@@ -665,11 +665,149 @@ __global__ __launch_bounds__(256) void border_sweep_kernel(const double* __restr
     for (int k = 0; k < NT; ++k) store_xtile_rows(Xc + 16 * k, ldx, lane, rows, xt[k]);
 }
 
+// ---------------------------------------------------------------------------
+// back_sweep: X (rows, ncols) <- X * L^-1 for a fused factor L (ncols x ncols): row i becomes L^-T x_i, the backward
+// counterpart of border_sweep for any number of rows (the predictive variance's gradient wants w = L^-T v for every test
+// point).  The product is X L, not X L^T, so the summation index runs down the ROWS of L.  The tile product stays
+// tile_mma's, Y[c][n] = sum_k M[c][k] X[n][k], with M = -L_(kc)^T: the <= 16 rows of X remain the B operand and the result
+// comes back in X layout (it feeds the next product from its registers), and the A operand is read straight from memory
+// TRANSPOSED -- a_v(lane) = -L[kap(lane >> 4, v)][rho(lane & 15)]: one 8-byte load per fragment element, the 16 lanes of
+// a group covering one row's 128 bytes between them (a permutation of them), four rows per load instruction.
+// One launch per 128-column block t, from the last to the first, t + 1 workgroups per 16-row group (blockIdx.y): workgroup
+// b updates column block c = t - b with the block the launch before solved, X_c -= X_(t+1) L_(t+1, c), wave w its tiles w
+// and 4 + w; workgroup 0 (c == t) then solves X_t <- X_t L_tt^-1 by the backward recurrence over the eight tiles, for
+// j = 7 .. 0:  X_j <- X_j W_jj;  X_k -= X_j L_jk for k < j (one wave, 36 tile products), from operands staged in LDS: the
+// transposed off-diagonal tiles, negated, and W_jj^T -- which is the stored diagonal tile as it lies in memory, strict
+// upper part, with 1 / diag(L) on the diagonal and zeros below.  Launch t - 1 finds X_t final.  The order is the launch
+// order; no workgroup waits for another, nothing is added atomically: the same bits every run.  The chain is ncols / 128
+// launches whatever `rows` is; every row group streams L's lower triangle once per chain (groups beyond the first mostly
+// out of L2).  Dead rows of the last group are fed as zeros and never stored.
+// Reads of L: exactly what border_sweep reads -- the tiles below the block diagonal, and of the diagonal 128 x 128 blocks
+// the lower 16 x 16 tiles and the diagonal tiles whole; never the block-upper tiles.
+// ---------------------------------------------------------------------------
+// x[v] = T[fr][kap(fg, v)] of the TRANSPOSE T of the 16 x 16 tile at p: X layout of L_jk^T for publish_tile
+__device__ __forceinline__ void load_xtile_t(const double* p, int64_t ld, int lane, double (&x)[4]) {
+    const int fr = lane & 15, fg = lane >> 4;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) x[v] = p[(int64_t)kap(fg, v) * ld + fr];
+}
+// A-operand fragments of -M^T for the 16 x 16 tile M at `tile` in memory: a[v] = -M[kap(lane >> 4, v)][rho(lane & 15)]
+__device__ __forceinline__ void load_afrag_t_neg(const double* tile, int64_t ld, int lane, double (&a)[4]) {
+    const int i = lane & 15, kk = lane >> 4;
+    const int col = kap(i & 3, i >> 2);                     // rho(i)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) a[v] = -tile[(int64_t)kap(kk, v) * ld + col];
+}
+// slot of tile (j, k), k <= j, of the staged diagonal block
+__device__ __forceinline__ constexpr int back_slot(int j, int k) { return j * (j + 1) / 2 + k; }
+
+__global__ __launch_bounds__(256) void back_sweep_kernel(const double* __restrict__ L, int64_t ldl, double* X, int64_t ldx,
+                                                         int64_t rows_all, int64_t t, int has_next) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    d2* tiles = reinterpret_cast<d2*>(smem);
+    double* xs = reinterpret_cast<double*>(smem + NTILES * TILE_BYTES);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t cb = t - blockIdx.x;                      // the column block of X (and of L) of this workgroup
+    const bool solver = blockIdx.x == 0;
+    const int64_t row0 = (int64_t)16 * blockIdx.y;
+    const int rows = (int)(rows_all - row0 < 16 ? rows_all - row0 : 16);
+    X += row0 * ldx;
+    if (solver) {
+        // the 28 tiles below the diagonal of L_tt, transposed and negated, round-robin over the waves; the eight
+        // diagonal tiles as W^T: the tile as stored above its diagonal, 1 / diag on it, zero below
+        const double* Lb = L + (int64_t)PB * t * (ldl + 1);
+        int q = 0;
+#pragma unroll
+        for (int j = 1; j < NT; ++j)
+#pragma unroll
+            for (int k = 0; k < j; ++k) {
+                if ((q & 3) == wave) {
+                    double x[4];
+                    load_xtile_t(Lb + (int64_t)(16 * j) * ldl + 16 * k, ldl, lane, x);
+                    publish_tile(tiles + back_slot(j, k) * 128, lane, x, -1.0);
+                }
+                ++q;
+            }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = wave + 4 * r;
+            const double* Ljj = Lb + (int64_t)(16 * j) * (ldl + 1);
+            const int n = lane & 15, fg = lane >> 4;
+            double x[4];
+            load_xtile(Ljj, ldl, lane, x);                  // x[v] = G[n][kap(fg, v)]
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int k = kap(fg, v);
+                x[v] = (k > n) ? x[v] : (k == n) ? rcp_newton(x[v]) : 0.0;
+            }
+            publish_tile(tiles + back_slot(j, j) * 128, lane, x, 1.0);
+        }
+    }
+
+    double* Xc = X + (int64_t)PB * cb;
+    double acc[2][4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) load_xtile_rows(Xc + 16 * (wave + 4 * p), ldx, lane, rows, acc[p]);
+    if (has_next) {
+        const double* Xk = X + (int64_t)PB * (t + 1);
+        double xk[NT][4];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) load_xtile_rows(Xk + 16 * j, ldx, lane, rows, xk[j]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            // rows of block t + 1 of L, the 16 columns of this wave's tile of block cb
+            const double* Lr = L + ((int64_t)PB * (t + 1)) * ldl + (int64_t)PB * cb + 16 * (wave + 4 * p);
+            double a[NT][4];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) load_afrag_t_neg(Lr + (int64_t)(16 * j) * ldl, ldl, lane, a[j]);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) tile_mma(a[j], xk[j], acc[p]);
+        }
+    }
+    if (!solver) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) store_xtile_rows(Xc + 16 * (wave + 4 * p), ldx, lane, rows, acc[p]);
+        return;
+    }
+    // workgroup 0: the updated block to wave 0 through LDS (lane-private slots), then the backward recurrence on it
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xs[((wave + 4 * p) * 64 + lane) * 4 + v] = acc[p][v];
+    __syncthreads();
+    if (wave != 0) return;
+    double xt[NT][4];
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xt[k][v] = xs[(k * 64 + lane) * 4 + v];
+#pragma unroll
+    for (int j = NT - 1; j >= 0; --j) {
+        double a[4], z[4] = {0., 0., 0., 0.};
+        load_afrag(tiles + back_slot(j, j) * 128, lane, a);
+        tile_mma(a, xt[j], z);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) xt[j][v] = z[v];
+#pragma unroll
+        for (int k = 0; k < j; ++k) {
+            double b[4];
+            load_afrag(tiles + back_slot(j, k) * 128, lane, b);
+            tile_mma(b, xt[j], xt[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int k = 0; k < NT; ++k) store_xtile_rows(Xc + 16 * k, ldx, lane, rows, xt[k]);
+}
+
 static hipError_t panel_mfma_attrs() {
     static PerDeviceOnce once;
     return once.run([]() -> hipError_t {
         hipError_t es = hipFuncSetAttribute((const void*)border_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             SWEEP_LDS);
+        if (es != hipSuccess) return es;
+        es = hipFuncSetAttribute((const void*)back_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEP_LDS);
         if (es != hipSuccess) return es;
         hipError_t e = hipFuncSetAttribute((const void*)trsm128_kernel<-1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            NTILES * TILE_BYTES);
@@ -719,6 +857,22 @@ hipError_t launch_border_sweep(hipStream_t s, const double* L, int64_t ldl, int6
     const int64_t nblk = ncols / PB;
     for (int64_t t = 0; t < nblk; ++t)
         hipLaunchKernelGGL(border_sweep_kernel, dim3((unsigned)(nblk - t)), dim3(256), SWEEP_LDS, s, L, ldl, X, ldx, (int)rows, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_back_sweep(hipStream_t s, const double* L, int64_t ldl, int64_t ncols, double* X, int64_t ldx,
+                             int64_t rows) {
+    if (rows < 1 || (rows + 15) / 16 > 65535 || ncols < 0 || ncols % PB || ldl % 2 || ldx % 2 || ldl < ncols || ldx < ncols ||
+        (reinterpret_cast<uintptr_t>(L) & 15) || (reinterpret_cast<uintptr_t>(X) & 15))
+        return hipErrorInvalidValue;
+    if (ncols == 0) return hipSuccess;
+    hipError_t e = panel_mfma_attrs();
+    if (e != hipSuccess) return e;
+    const int64_t nblk = ncols / PB;
+    const unsigned groups = (unsigned)((rows + 15) / 16);
+    for (int64_t t = nblk - 1; t >= 0; --t)
+        hipLaunchKernelGGL(back_sweep_kernel, dim3((unsigned)(t + 1), groups), dim3(256), SWEEP_LDS, s, L, ldl, X, ldx, rows, t,
+                           t + 1 < nblk ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -47,7 +47,7 @@ int fail_gave_up(const char* api) {
 // The end of a call that ran backward_solve_resident, behind the caller's own device-to-host copies: the read of the
 // one-launch solve's "a poll gave up" word where that solve ran, the call's one synchronisation, the timers, and the
 // word's status under the caller's API name
-static int solve_epilogue(gpmi_ctx* c, const char* api) {
+int solve_epilogue(gpmi_ctx* c, const char* api) {
     hipStream_t s = c->stream;
     int gave_up = 0;
     if (c->res.factor_fused && tuning().trsv_vinv >= 2)

@@ -273,6 +273,12 @@ class HipBlockOps:
         check(self.lib.gpmi_dev_border_sweep(self._stream(), self._p(L), self._ld(L), L.shape[0] if ncols is None else ncols,
                                              self._p(X), self._ld(X), X.shape[0] if rows is None else rows))
 
+    def back_sweep(self, L, X, rows=None, ncols=None):
+        """X (any number of rows) <- X L^-1 for a fused factor L (row i becomes L^-T x_i): the backward sweep behind
+        GPContext.predict_grad"""
+        check(self.lib.gpmi_dev_back_sweep(self._stream(), self._p(L), self._ld(L), L.shape[0] if ncols is None else ncols,
+                                           self._p(X), self._ld(X), X.shape[0] if rows is None else rows))
+
     def gemm_nt(self, Cm, A, B):
         check(self.lib.gpmi_dev_gemm_nt(self._stream(), self._p(Cm), self._ld(Cm), self._p(A), self._ld(A),
                                         self._p(B), self._ld(B), Cm.shape[0], Cm.shape[1], A.shape[1], 0, 0))

@@ -332,6 +332,20 @@ class GPContext:
         self.set_test(Xs)
         return self.predict_resident(want_sd)
 
+    def predict_grad(self, Xs=None, want_var_grad=True):
+        """Mean, variance and their gradients with respect to the test inputs at the resident regression fit:
+        (mu (n,), var (n,), dmu (n, d), dvar (n, d) or None when it was not asked for).  Xs given: set_test first;
+        otherwise the resident test set.  The derivatives are with respect to the raw inputs, whatever lengthscales
+        are set; d sd = dvar / (2 sd) is the caller's.  Kernels 'rbf' and the Materns, d <= 32."""
+        if Xs is not None:
+            self.set_test(Xs)
+        mu = np.empty(self.n)
+        var = np.empty(self.n)
+        dmu = np.empty((self.n, self.d))
+        dvar = np.empty((self.n, self.d)) if want_var_grad else None
+        check(self._lib.gpmi_predict_grad_resident(self._h, ptr(mu), ptr(var), ptr(dmu), ptr(dvar) if want_var_grad else None))
+        return mu, var, dmu, dvar
+
     def fit_predict_resident(self, sigma, l, noise_var, want_sd=True):
         """prediction() in one pass (GP_regression.py:109-156) for the resident training and test sets: the rows
         K(X*, X) ride through the Cholesky below the y row.  Returns (lml, mu, sd_or_var)."""

@@ -91,7 +91,10 @@ int gpmi_ctx_destroy(gpmi_ctx* ctx);
  *               -1 by size -- the default --, 0 the padded 128-row sweep, 1 the <= 16-row sweep kernel whenever allowed);
  *               gpmi_remove: "remove_keep_spare" (default 0: the buffer a removal leaves behind is freed; 1: it is kept
  *               as the target of the next removal, so a remove / append cycle allocates nothing; any fit drops it, and
- *               so does setting the option back to 0).
+ *               so does setting the option back to 0);
+ *               gpmi_predict_grad_resident: "pgrad_sweep" (-1 by size -- the default --, 0 the inverse route, 1 the
+ *               backward sweep whenever the factor is fused), "pgrad_sweep_max" (default 4096: the largest n
+ *               that takes the sweep under "by size"; profiles/r17_predgrad_rate.txt).
  * The context-free gpmi_dev_* primitives run with the defaults. */
 int gpmi_set_option(gpmi_ctx* ctx, const char* name, int64_t value);
 
@@ -254,6 +257,38 @@ int gpmi_post_chol(gpmi_ctx* ctx, double jitter, double* L_out, int64_t* bad_piv
  * gpmi_fit_predict_sample_resident or an earlier call formed it for this jitter, else formed now (status and bad_pivot as
  * gpmi_post_chol).  Row sums are added in a fixed order (bitwise reproducible); against np.dot they differ by rounding. */
 int gpmi_post_sample(gpmi_ctx* ctx, double jitter, const double* Z, int64_t num_fun, double* LZ_out, int64_t* bad_pivot);
+
+/* Gradients of the predictive mean and variance with respect to the test inputs, at the resident regression
+ * factorisation and the resident test set (gpmi_set_test).  With z = x / r (r: gpmi_set_lengthscales, all 1 when none
+ * are set), k_j = k(z*, z_j), alpha = K_y^-1 y and w = K_y^-1 k = L^-T v, v = L^-1 k:
+ *   dmu/dx*_k  =      sum_j alpha_j D_jk            dvar/dx*_k = -2 sum_j w_j D_jk
+ *   D_jk = dk_j/dx*_k = -k_j (z*_k - z_jk) / (l^2 r_k)                     kind 0
+ *                      = -sigma^2 a^2 H(t_j) (z*_k - z_jk) / r_k            kinds 4, 5, 6 (a, t, H as at gpmi_lml_grad)
+ * (the prior term sigma^2 of var does not depend on x* for these kinds).  An element with sq_j == 0 contributes 0; for
+ * nu = 1/2 the kernel has no derivative there.  The derivatives are with respect to the raw, unscaled x* as the caller
+ * passed it (gpmi_sparse_grad treats Z the same way).
+ * mu, var: n doubles each, bit for bit what gpmi_predict_resident(want_sd = 0) computes from the same v.  dmu, dvar:
+ * n x d row-major.  Every pointer may be NULL.  There is no want_sd: dsd = dvar / (2 sd) is the caller's.
+ * v: formed exactly as gpmi_predict_resident forms it when it is not resident (and left resident); reused when it is,
+ * wherever it lies (in V, or below the y row after the one-pass and augmented fits).  It is never written:
+ * gpmi_post_chol, gpmi_post_sample and gpmi_predict_resident return the same bits before and after.
+ * W (row i: w_i) goes to a buffer of the context's own (n_p x (N_p + ld_pad) doubles, grown on demand, released by the
+ * next fit) by one of two routes, chosen by gpmi_pgrad_plan.h:
+ *   sweep    a copy of v through gpmi_dev_back_sweep: O(N^2 n), no N^3 term; a fused factor only;
+ *   inverse  U = L^-T by the forward sweep on the identity (N^3 / 3, the buffer of gpmi_lml_grad), W = V U^T by the routed
+ *            GEMM; serves a first-generation factor ("panel_fused" 0 at fit time) and large n.
+ * Options: "pgrad_sweep" -1 by size (the default), 0 always the inverse route, 1 the sweep route whenever allowed;
+ * "pgrad_sweep_max" the largest n that takes the sweep route under "by size" (default 4096: the largest measured n at
+ * which the sweep wins at N = 16384, d = 8 -- 62.2 against 62.7 ms there, 3.02 against 31.8 ms at n = 16;
+ * profiles/r17_predgrad_rate.txt).  With
+ * dvar == NULL nothing is swept backwards: the call costs alpha and one O(n N d) pass.
+ * The pass regenerates K(X*, X) on the fly (never stored), reads W once and adds per-(row, 1024-column chunk) partial
+ * sums in index order: no atomics, the same bits every run.
+ * GPMI_ERR_BAD_ARG, nothing changed: no regression factorisation resident, no test set, a kernel kind other than 0, 4, 5,
+ * 6, d > 32 (a test point's 2 d sums are kept in registers, as in gpmi_sparse_grad).  The single-launch backward solve's
+ * give-up word is reported as by gpmi_get_alpha.  Timers: GPMI_T_ALPHA alpha, GPMI_T_KS and GPMI_T_SOLVE_V v and the
+ * route to W, GPMI_T_MEANVAR the row dots and the pass. */
+int gpmi_predict_grad_resident(gpmi_ctx* ctx, double* mu, double* var, double* dmu, double* dvar);
 
 /* Gradient of the log marginal likelihood at the resident factorisation:
  *   d_ell   = .5 * trace((alpha alpha^T - K_y^-1) @ l_grad),     l_grad     = sigma^2 exp(-.5 sqdist/l^2) sqdist/l^3
@@ -597,6 +632,21 @@ int gpmi_dev_trsm_block(void* stream, const double* L_dev, int64_t ldl, double* 
  * from ncols on are neither read nor written; L is not written.  Anything else is refused with nothing launched. */
 int gpmi_dev_border_sweep(void* stream, const double* L_dev, int64_t ldl, int64_t ncols, double* X_dev, int64_t ldx,
                           int64_t rows);
+/* X (rows x ncols, ldx) <- X * L^-1 for rows >= 1 and L the ncols x ncols lower factor (ldl) of a FUSED factorisation: row
+ * i becomes L^-T x_i, the backward counterpart of gpmi_dev_border_sweep with the same argument rules (ncols a multiple of
+ * 128, ldl and ldx even and >= ncols, both pointers 16-byte aligned; ncols == 0 does nothing).  One launch per 128-column
+ * block from the last to the first whatever `rows` is: rows beyond 16 are further 16-row groups in the same launches
+ * (a second grid dimension), dead rows of the last group are fed as zeros and never stored.  In launch t the workgroup of
+ * column block c <= t applies X_c -= X_(t+1) L_(t+1, c); the one with c == t then solves X_t <- X_t L_tt^-1 by the
+ * backward recurrence over its eight 16 x 16 tiles with the stored tile inverses.  No workgroup waits for another, nothing
+ * is added atomically, the sums run in a fixed order: the same bits every run.  L is streamed once per 16-row group.  Reads
+ * of L: exactly those of gpmi_dev_border_sweep -- never the block-upper tiles.  Rows of X from `rows` on and columns from
+ * ncols on are neither read nor written; L is not written.  Anything else is refused with nothing launched.  Measured
+ * (profiles/r17_predgrad_rate.txt): with one row group the chain of launches bounds it, 15.7 us per launch at 4096 columns
+ * and 20.4 us at 65536, where it reads L at 0.26 of the streaming-read rate; with 256 row groups a launch takes 134 us to
+ * 1.8 ms and the groups read L, mostly out of L2, at 0.66 to 0.75 of that rate. */
+int gpmi_dev_back_sweep(void* stream, const double* L_dev, int64_t ldl, int64_t ncols, double* X_dev, int64_t ldx,
+                        int64_t rows);
 /* C (M x N, ldc) -= A (M x K, lda) * B (N x K, ldb)^T.  lower != 0: only tiles
  * that intersect {col <= row + diag_off} are touched. */
 int gpmi_dev_gemm_nt(void* stream, double* C_dev, int64_t ldc, const double* A_dev, int64_t lda,
